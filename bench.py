@@ -98,11 +98,18 @@ def parse(argv=None):
                     help="N = 1: do not run the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic in this run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: workers rendezvous over gloo, all-reduce their ranks and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline path: after the run, write what the timed path computed as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all; larger outputs as a fixed seeded row sample + <name>_rows.npy): the per-step losses of the timed "
+                         "steps and the embedding tables after the last one, and the last timed evaluation's top-K lists and target ranks")
     a = ap.parse_args(argv)
     if a.workload is None:
         a.workload = "ml1m"          # the metric's own workload for EVERY N: the 1 -> 8 series is one quantity
     if a.parallel is None:
         a.parallel = "rows" if (a.force_collectives and a.gpus == 1) else "replicas"
+    if a.dump_outputs and (a.workflow or a.dry_run or (a.parallel in ("rows", "rows2d") and (a.gpus > 1 or a.force_collectives))):
+        ap.error("--dump-outputs writes the headline path's outputs (one GPU or independent replicas); not with --workflow, --dry-run "
+                 "or a sharded top-level job")
     if a.dim is None:
         a.dim = 128 if a.workload == "yelp" else 64
     small = a.workload in ("ml1m", "tiny") and a.parallel == "replicas"
@@ -200,6 +207,27 @@ def oracle_replay(d, graph, layers, batch, triplets, user0, item0, n_steps):
         losses.append(orc.lightgcn_step(csr, user, item, st, users[sl], pos[sl], neg[sl], layers))
     return {"losses": np.asarray(losses, dtype=np.float64), "user": user, "item": item, "seconds": time.perf_counter() - t0,
             "steps": n_steps}
+
+
+def write_outputs(out_dir, arrays, budget=60 << 20, seed=0):
+    """--dump-outputs: `arrays` (name -> numpy array) as out_dir/<name>.npy -- float32 stays float32, everything else becomes
+    float64 (integer ids and counts are exact there).  If the whole exceeds `budget` bytes, every array above 1 MB keeps the
+    same fraction of its rows, drawn by a generator seeded with (seed, n_rows) -- arrays with the same row count keep
+    the same rows -- and the kept row indices go to <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: (v if v.dtype == np.float32 else v.astype(np.float64)) for k, v in arrays.items()}
+    cut = {k for k, v in arrays.items() if v.nbytes > (1 << 20) and v.shape[0] > 1}
+    fixed = sum(v.nbytes for k, v in arrays.items() if k not in cut)
+    var = sum(v.nbytes + 8 * v.shape[0] for k, v in arrays.items() if k in cut)    # (+ the float64 row index of every kept row)
+    frac = 1.0 if fixed + sum(arrays[k].nbytes for k in cut) <= budget else max(budget - fixed, 0) / var
+    for name, v in arrays.items():
+        if frac < 1.0 and name in cut:
+            n = v.shape[0]
+            rows = np.sort(np.random.default_rng([seed, n]).choice(n, size=max(1, int(n * frac)), replace=False))
+            v = v[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
 
 
 def relerr_max(a, b):
@@ -975,6 +1003,10 @@ def worker(args, traffic_live=None):
     timed_partials = partials.clone()     # (the handle's loss buffer is reused by the next call)
     timed_tables = (tuple(p_.detach().cpu().numpy().copy() for p_ in (victim.embedding_user.weight, victim.embedding_item.weight))
                     if want_parity and args.warmup + args.steps == n_par else None)
+    dump = {}
+    if args.dump_outputs and rank == 0:   # (device-side copies: the repeat below trains the tables further)
+        dump["step_losses"] = timed_partials.double().sum(dim=1)
+        dump["user_embedding"], dump["item_embedding"] = (p_.detach().clone() for p_ in (victim.embedding_user.weight, victim.embedding_item.weight))
     # the GPU-side span of such a call, measured on a REPEAT of it behind the timed one (round 5 recorded its start event inside the
     # timed region: 6.6 us of host time in front of the launch with the device waiting; the span is diagnostic, the repeat costs nothing)
     span_cols = timed_cols if args.steps <= 64 else tuple(t[: 64 * B] for t in timed_cols)
@@ -1067,6 +1099,9 @@ def worker(args, traffic_live=None):
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             ev_el = float(t.item())
         hr50 = float(res["hit_counts"][0, 2].item()) / max(len(ev_users), 1)
+        if args.dump_outputs and rank == 0:   # the last timed evaluation, read back now (the next session run overwrites its buffers;
+            dump["eval_users"] = np.asarray(ev_users)   # a synchronous copy, so nothing of it is queued into the latency measured below)
+            dump.update({k: res[k].cpu().numpy() for k in ("top_ids", "top_scores", "target_score", "target_rank", "hit_counts")})
         t1 = time.perf_counter()  # one evaluation on an idle device through the plain call, host enqueue included (latency, not throughput)
         res = full_catalog_topk(victim, ev_dev, ptr_dev, idx_dev, tg_dev, K=100, chunk=ev_chunk, to_host=False)
         hit_counts(res["target_rank"], (10, 20, 50, 100)).cpu()
@@ -1142,6 +1177,9 @@ def worker(args, traffic_live=None):
             "timed_region": timed_region, "epoch_with_sampler": epoch_obj, "topk": topk, "roofline": roofline, "cpu_baseline": cpu_aten,
             "cpu_baseline_port": cpu, "parity": parity, "also": also, "mfma_gemm": mfma, "ranks_seen": seen, "last_step_loss": last_loss,
         }
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in dump.items()})
+        del dump
 
     # ================= N > 1: the strong-scaling legs (ONE job sharded over the ranks) go into `also`, under a deadline
     if world > 1 and not args.no_also_sharded:

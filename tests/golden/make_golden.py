@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Generate the golden input/output vectors under tests/golden/ by IMPORTING the
-reference (gusye1234/recad @ /root/reference) in the build container.
+reference (gusye1234/recad v0.0.2, a checkout passed as --reference).
 
 This script is the provenance of every ``*.npz`` in this directory.  It is run
-by hand in the container that has ``/root/reference`` (the GPU box does not);
+by hand on a machine that has a checkout of the reference;
 nothing under ``tests/`` or the product imports it.  It copies no reference
 source: it drives the reference's public objects
 
@@ -15,7 +15,7 @@ sampler produced) and outputs (per-step loss, step-1 gradients, tables, scores,
 top-K lists, HR@K rows).
 
 Usage:
-    python tests/golden/make_golden.py [--scratch /tmp/recad_golden_scratch]
+    python tests/golden/make_golden.py --reference PATH [--scratch /tmp/recad_golden_scratch]
 
 Determinism: the reference is bit-reproducible only with 1 intra-op thread
 (SURVEY.md section 8c), so we pin ``torch.set_num_threads(1)``.
@@ -28,7 +28,6 @@ import zipfile
 
 import numpy as np
 
-REF = "/root/reference"
 OUT = os.path.dirname(os.path.abspath(__file__))
 
 
@@ -430,17 +429,19 @@ def golden_graph_inject(recad, torch, name, tag):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--reference", required=True, help="checkout of the reference (gusye1234/recad v0.0.2): its recad/ and data/")
     ap.add_argument("--scratch", default="/tmp/recad_golden_scratch")
     ap.add_argument("--only", default="")
     args = ap.parse_args()
+    ref_root = os.path.abspath(args.reference)
     os.makedirs(os.path.join(args.scratch, "data"), exist_ok=True)
     if not os.path.exists(os.path.join(args.scratch, "data", "dev")):
-        shutil.copytree(os.path.join(REF, "data", "dev"), os.path.join(args.scratch, "data", "dev"))
+        shutil.copytree(os.path.join(ref_root, "data", "dev"), os.path.join(args.scratch, "data", "dev"))
     if not os.path.exists(os.path.join(args.scratch, "data", "game")):
-        with zipfile.ZipFile(os.path.join(REF, "data", "game.zip")) as z:
+        with zipfile.ZipFile(os.path.join(ref_root, "data", "game.zip")) as z:
             z.extractall(os.path.join(args.scratch, "data"))
     os.chdir(args.scratch)  # reference resolves ./data and ./generated from cwd
-    sys.path.insert(0, REF)
+    sys.path.insert(0, ref_root)
     import torch
 
     torch.set_num_threads(1)
