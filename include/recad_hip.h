@@ -481,6 +481,40 @@ int rk_ncf_train_epoch(const rk_ncf_desc *desc, const int64_t *users, const int6
                        const int64_t *labels, int64_t n, int32_t batch, int32_t adam_t0,
                        float *loss_partials, int32_t apply_update, void *stream);
 
+/* ---------------------------------------------------------------- defender --------- */
+/* PCASelectUsers (recad/model/defense/PCASelectUsers.py:47-93, registry recad/default.py:223-228) without the dense
+ * U x I array and the I x I covariance: C.X = D^-1 A^T (A (D^-1 X)), A the U x I rating CSR, D = diag(sigma_j).
+ * All device pointers; asynchronous on `stream` unless stated otherwise.  recad_amd/defense/pca_select_users.py drives
+ * them (block subspace iteration with Rayleigh-Ritz replaces scipy.sparse.linalg.eigs, PCASelectUsers.py:66). */
+
+/* A^T as a CSR (n_cols rows, users ascending inside a row): radix sort of (col << 32 | row) keys with the values as
+ * payload and stream-ordered temporaries.  Reads rowptr[n_rows] back (synchronous).  Replaces the csr_matrix(dataArray)
+ * / np.transpose of PCASelectUsers.py:61-64. */
+int rk_pca_transpose(int32_t n_rows, int32_t n_cols, const int32_t *rowptr, const int32_t *col, const float *val,
+                     int32_t *t_rowptr /*[n_cols+1]*/, int32_t *t_col /*[nnz]*/, float *t_val /*[nnz]*/, void *stream);
+/* sklearn.preprocessing.scale(csr, axis=0, with_mean=False) (PCASelectUsers.py:62): per column the population variance
+ * over all n_users rows (zeros included) in fp64, rounded to fp32; var < 10 * FLT_EPSILON -> 1.  inv_scale[j] = 1 / sigma_j;
+ * sigma (optional) = sigma_j.  From the rows of A^T (rk_pca_transpose), deterministic. */
+int rk_pca_col_scale(int32_t n_cols, int32_t n_users, const int32_t *t_rowptr, const float *t_val, float *inv_scale /*[n_cols]*/,
+                     float *sigma /*[n_cols] or NULL*/, void *stream);
+/* Y = diag(r_out) . A . diag(c_in) . X for X row-major [n_cols, b], Y [n_rows, b], b in {8, 16}; c_in / r_out may be
+ * NULL (no scale).  X and Y 16-byte aligned.  One half of the covariance product covSM = S^T S (PCASelectUsers.py:64-66). */
+int rk_pca_spmm(int32_t n_rows, const int32_t *rowptr, const int32_t *col, const float *val, const float *c_in,
+                const float *r_out, int32_t b, const float *X, float *Y, void *stream);
+/* dist[u] = sum_e val[e]^2 * w[col[e]], w[j] = sum_{c < k} V[j * ldv + c] (w written to `w`, [n_cols]): the distances
+ * np.dot(dataArray**2, real(vecs)) summed over the k columns (PCASelectUsers.py:68-78), fp64 accumulation. */
+int rk_pca_sq_spmv(int32_t n_rows, int32_t n_cols, const int32_t *rowptr, const int32_t *col, const float *val, const float *V,
+                   int32_t ldv, int32_t k, float *w, float *dist /*[n_rows]*/, void *stream);
+/* G = Z^T Z, Z = [P | Q] (P [n, p], Q [n, q] row-major, Q may be NULL with q = 0, p + q <= 32), fp64, G [(p+q)^2]
+ * row-major.  part: double[RK_PCA_GRAM_BLOCKS * (p+q)^2] scratch.  Fixed reduction order (deterministic). */
+#define RK_PCA_GRAM_BLOCKS 256
+int rk_pca_gram(int64_t n, const float *P, int32_t p, const float *Q, int32_t q, double *part, double *G, void *stream);
+/* out = V . M, V [n, p] fp32, M [p, q] fp64 (device), out [n, q] fp32 (not aliasing V); p, q <= 32. */
+int rk_pca_update(int64_t n, const float *V, int32_t p, const double *M, int32_t q, float *out, void *stream);
+/* order[0..m) = the ids of the m smallest dist, ties to the lower id: Python's stable sorted(..., key=dist) of
+ * PCASelectUsers.py:80 (one 64-bit radix key per user).  Synchronous; RK_EINVAL when a distance is not finite. */
+int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *order, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

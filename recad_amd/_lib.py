@@ -17,6 +17,7 @@ RK_LOSS_PARTIALS = 256
 RK_MAX_GRAPH_STEPS = 64
 ABI_VERSION = 9
 RK_LDS_SYNC_WORDS = 2560
+RK_PCA_GRAM_BLOCKS = 256
 
 
 class HipLibraryMissing(RuntimeError):
@@ -170,6 +171,13 @@ _SIGNATURES = {
     "rk_ncf_train_epoch": [C.POINTER(NCFDesc), _P, _P, _P, _I64, _I32, _I32, _P, _I32, _P],
     "rk_mf_train_epoch": [_I32, _I32, _I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _F,
                           _F, _P, _I32, _F, C.c_uint64, _P],
+    "rk_pca_transpose": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P],
+    "rk_pca_col_scale": [_I32, _I32, _P, _P, _P, _P, _P],
+    "rk_pca_spmm": [_I32, _P, _P, _P, _P, _P, _I32, _P, _P, _P],
+    "rk_pca_sq_spmv": [_I32, _I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P],
+    "rk_pca_gram": [_I64, _P, _I32, _P, _I32, _P, _P, _P],
+    "rk_pca_update": [_I64, _P, _I32, _P, _I32, _P, _P],
+    "rk_pca_select": [_I32, _P, _I32, _P, _P],
 }
 _RESTYPES = {"rk_last_error": C.c_char_p}
 EXPORTS = tuple(_SIGNATURES)

@@ -1,7 +1,7 @@
 """Default configuration registry for the victim path.
 
-Mirrors the keys and values of the reference's registry for the three victims
-(recad/default.py:103-132) and the implicit dataset / workflow knobs the hot path reads
+Mirrors the keys and values of the reference's registry for the three victims and the
+PCASelectUsers defender (recad/default.py:103-132,223-228) and the implicit dataset / workflow knobs the hot path reads
 (recad/default.py:49-62,247-267).  Only what the path needs is present.
 """
 import logging
@@ -25,6 +25,8 @@ MODEL = {
         },
     },
     "attacker": {"random": {"attack_num": 50, "filler_num": 36}},
+    # recad/default.py:223-228; block / tol / max_iter / seed are this build's solver knobs (block None = 8, or 16 when kVals > 5)
+    "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED}},
 }
 for _scope in MODEL.values():
     for _cfg in _scope.values():

@@ -38,8 +38,10 @@ def _guard(fn):
 
 
 class BaseVictim(nn.Module):
-    #: key into default.MODEL["victim"]; set by subclasses
+    #: key into default.MODEL[scope]; set by subclasses
     victim_name = None
+    #: default.MODEL scope of the subclass ("victim"; the defenders reuse this lazy-init contract with "defender")
+    scope = "victim"
     #: kwargs the caller supplies at .I() time (not in the defaults)
     user_args = "dataset"
 
@@ -61,8 +63,8 @@ class BaseVictim(nn.Module):
     @classmethod
     def from_config(cls, **kwargs):
         name = cls.victim_name
-        assert name in MODEL["victim"], f"{name} is not on the default victim models"
-        defaults = MODEL["victim"][name]
+        assert name in MODEL[cls.scope], f"{name} is not on the default {cls.scope} models"
+        defaults = MODEL[cls.scope][name]
         config = {k: copy(v) for k, v in defaults.items()}
         allowed = set(config) | set(parse_args(cls.user_args)) | set(parse_args(cls.extra_user_args(kwargs)))
         for k, v in kwargs.items():

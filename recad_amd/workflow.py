@@ -243,7 +243,11 @@ class Defense(Normal):
         results["attacked"] = self.normal_evaluate(self.victim, fake_victim, self.victim_data, self.c["target_id_list"], self.c["topks"])
         if "train_step" in self.defender.input_describe():
             self.normal_train(self.defender, self.c["defense_epoch"])
-        flagged = list(self.defender.defense_step())
+        # a defender whose defense_step takes a dataset (PCASelectUsers) is shown the poisoned graph it is meant to clean
+        if "dataset" in (self.defender.input_describe().get("defense_step") or {}):
+            flagged = list(self.defender.defense_step(dataset=fake_dataset))
+        else:
+            flagged = list(self.defender.defense_step())
         cleaned = self.victim_data.delete_data("explicit", flagged, fake_array, filter_num=self.c["filter_num"])
         self.random_seed_set()
         defended_victim = self.victim.reset().I(dataset=cleaned).to(dev)
