@@ -515,6 +515,82 @@ int rk_pca_update(int64_t n, const float *V, int32_t p, const double *M, int32_t
  * PCASelectUsers.py:80 (one 64-bit radix key per user).  Synchronous; RK_EINVAL when a distance is not finite. */
 int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *order, void *stream);
 
+/* ---------------------------------------------------------------- attacker --------- */
+/* AUSH (recad/model/attacker/aush.py, registry recad/default.py:159-168) without the dense U x I train_mat
+ * (explicit.py:102,134-143) and the dense B x I batches (explicit.py:178-199, aush.py:92-134): each attack row is the sparse
+ * set "fillers U S" of the rating CSR (rows sorted by item).  recad_amd/attack/aush.py drives these entries.  All
+ * pointers are device pointers and calls are asynchronous on `stream` unless stated otherwise.  Random draws come from
+ * rk_mix64 keyed on (seed, stream_id, row, draw). */
+#define RK_AUSH_HG 128            /* generator hidden width, Linear(I, 128) (aush.py:213-218) */
+#define RK_AUSH_HD 150            /* discriminator width, Linear(I, 150) and two Linear(150, 150) (aush.py:226-235) */
+#define RK_AUSH_MAX_FILLER 256    /* filler_num limit */
+#define RK_AUSH_MAX_SELECT 16     /* |selected_ids| limit */
+#define RK_AUSH_MAX_PAIRS 4096    /* batch * |selected_ids| limit (the ZR selection of one batch runs in one workgroup) */
+
+typedef struct rk_aush_desc {
+    int32_t n_users, n_items, filler_num, n_sel, batch, reserved;
+    const int32_t *rowptr, *col;   /* rating CSR [n_users + 1] / [nnz], item ids ascending inside a row */
+    const float *val;              /* ratings [nnz] */
+    const int32_t *sel;            /* selected_ids [n_sel] */
+    const float *g_w1t, *g_b1;     /* generator Linear(I, 128): weight transposed (item-major [n_items, 128]), bias [128] */
+    const float *g_w2, *g_b2;      /* generator Linear(128, I): weight [n_items, 128] (torch layout), bias [n_items] */
+    float *d_param, *d_m, *d_v;    /* the discriminator packed in one buffer, Adam moments alike: W1 transposed (item-major
+                                      [n_items, 150]), b1 [150], W2 [150, 150], b2, W3 [150, 150], b3, w4 [150], b4 [1] */
+    uint8_t *touched;              /* [n_items], zero-initialised: first-layer rows that ever had a gradient */
+    int32_t *touched_list;         /* [n_items]: those rows, in first-touch order */
+    int32_t *n_touched;            /* [1], zero-initialised */
+    int32_t *gslot;                /* [n_items], every entry -1 initially (and again after each step) */
+    void *work;                    /* rk_aush_workspace_bytes(batch, filler_num, n_sel) bytes */
+    int64_t work_bytes;
+    float lr, beta1, beta2, eps;   /* D's torch.optim.Adam (lr_d, aush.py:34-37) */
+} rk_aush_desc;
+
+/* Workspace of rk_aush_d_step / rk_aush_train_epoch (host only, no HIP call). */
+int rk_aush_workspace_bytes(int32_t batch, int32_t filler_num, int32_t n_sel, int64_t *bytes);
+/* The filler pool of each user -- rated items (value > 0) outside excl (sorted, = selected_ids U target_id_list),
+ * aush.py:63-70 -- as a CSR (pool_ptr [n_users + 1], pool_col [nnz]), and the users whose pool holds at least filler_num
+ * items, ascending, in eligible[0..*n_eligible): filler_filter_mat (utils.py:192-196) and aush.py:177-180.  Synchronous;
+ * *n_eligible is a host pointer. */
+int rk_aush_eligible(int32_t n_users, const int32_t *rowptr, const int32_t *col, const float *val, const int32_t *excl, int32_t n_excl,
+                     int32_t filler_num, int32_t *pool_ptr, int32_t *pool_col, int32_t *eligible, int32_t *n_eligible, void *stream);
+/* out = a permutation of in[0..n) by a radix sort of 64-bit random keys: np.random.permutation (explicit.py:189, aush.py:181). */
+int rk_aush_permute(int32_t n, const int32_t *in, uint64_t seed, uint64_t stream_id, int32_t *out, void *stream);
+/* sample_fillers (aush.py:60-77) for rows users[0..n_rows): filler_num draws with replacement from the user's pool (row index
+ * row0 + r in the RNG key), or the item ids draws[n_rows, filler_num] when draws != NULL (replay).  Duplicates collapse: the
+ * distinct fillers ascending in fcol[r, 0..nf[r]) with their ratings in fval (padding: item 2^31 - 1, rating 0); sval[r, s] =
+ * the rating at sel[s] (0 when unrated). */
+int rk_aush_sample(int32_t n_rows, const int32_t *users, int32_t filler_num, const int32_t *rowptr, const int32_t *col, const float *val,
+                   const int32_t *pool_ptr, const int32_t *pool_col, const int32_t *draws, uint64_t seed, uint64_t stream_id, int64_t row0,
+                   const int32_t *sel, int32_t n_sel, int32_t *fcol, float *fval, int32_t *nf, float *sval, void *stream);
+/* ZR_mask (aush.py:114-119) per batch of `batch` consecutive rows: of the n pairs (row, s) with sval == 0, exactly
+ * n - floor(n * (1 - zr_ratio)) (double arithmetic, as Python) get zr = 1, a uniform random subset. */
+int rk_aush_zr(int32_t n_rows, int32_t batch, int32_t n_sel, const float *sval, double zr_ratio, uint64_t seed, uint64_t stream_id,
+               uint8_t *zr, void *stream);
+/* gen[r, s] = 5 sigma(W2[sel_s] . sigma(W1 template_r + b1) + b2[sel_s]), the generator (aush.py:211-222) at S only; the
+ * template is the fillers of row r with their ratings (aush.py:126).  w1t is item-major [n_items, 128]. */
+int rk_aush_gen(int32_t n_rows, int32_t filler_num, const int32_t *fcol, const float *fval, const int32_t *nf, const float *w1t,
+                const float *b1, const float *w2, const float *b2, const int32_t *sel, int32_t n_sel, float *gen, void *stream);
+/* One batch of Aush.train_step (aush.py:128-167) on B <= desc->batch sampled rows: the discriminator step on
+ * real / fake = profile * (fillers_mask + selects_mask) with fake[S] = gen + 5 (target_patch at selected_ids, aush.py:121),
+ * torch.optim.Adam step adam_t on D (first-layer gradient reduced in (item, row) order: bit-reproducible), then
+ * losses[0..4) = d_loss, g_loss_rec, g_loss_shilling, g_loss_gan (with the updated D).  The generator is not changed
+ * (aush.py:138 detaches it).  The replay entry: the sample may come from rk_aush_sample with given draws and a given zr. */
+int rk_aush_d_step(const rk_aush_desc *desc, int32_t B, const int32_t *fcol, const float *fval, const int32_t *nf, const float *sval,
+                   const float *gen, const uint8_t *zr, int32_t adam_t, float *losses, void *stream);
+/* One epoch of Aush.train_step without a host round trip: permutation of eligible[0..n_eligible) (stream_id = epoch), filler
+ * draws, ZR masks and generator values for every row, then rk_aush_d_step per batch of desc->batch rows (the last one short),
+ * Adam steps adam_t0 + 1, ...; losses [n_batches, 4].  Row buffers: perm, nf [n_eligible], fcol / fval [n_eligible, filler_num],
+ * sval / gen / zr [n_eligible, n_sel]. */
+int rk_aush_train_epoch(const rk_aush_desc *desc, const int32_t *eligible, int32_t n_eligible, const int32_t *pool_ptr,
+                        const int32_t *pool_col, uint64_t seed, uint64_t epoch, double zr_ratio, int32_t adam_t0, int32_t *perm,
+                        int32_t *fcol, float *fval, int32_t *nf, float *sval, float *gen, uint8_t *zr, float *losses, void *stream);
+/* generate_fake's profiles (aush.py:187-206) into out [n_rows, n_items] (zero-filled first): the fillers' ratings, 5 at every
+ * target of every row, and at S round-half-even(gen (+ 5 where s is a target)) clipped to [1, 5]; pre (optional,
+ * [n_rows, n_sel]) receives the values before rounding. */
+int rk_aush_fake_assemble(int32_t n_rows, int32_t n_items, int32_t filler_num, const int32_t *fcol, const float *fval, const int32_t *nf,
+                          const int32_t *sel, int32_t n_sel, const float *gen, const int32_t *tgt, int32_t n_tgt, float *pre, float *out,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

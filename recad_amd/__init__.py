@@ -10,7 +10,7 @@ import random
 import numpy as np
 import torch
 
-from . import dataset, default, defense, model, utils, victim, workflow  # noqa: F401
+from . import attack, dataset, default, defense, model, utils, victim, workflow  # noqa: F401
 from .default import SEED
 
 random.seed(SEED)

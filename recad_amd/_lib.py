@@ -115,6 +115,24 @@ class NCFDesc(C.Structure):
     ]
 
 
+class AushDesc(C.Structure):
+    """rk_aush_desc (include/recad_hip.h)."""
+
+    _fields_ = [
+        ("n_users", C.c_int32), ("n_items", C.c_int32), ("filler_num", C.c_int32), ("n_sel", C.c_int32), ("batch", C.c_int32),
+        ("reserved", C.c_int32),
+        ("rowptr", C.c_void_p), ("col", C.c_void_p), ("val", C.c_void_p), ("sel", C.c_void_p),
+        ("g_w1t", C.c_void_p), ("g_b1", C.c_void_p), ("g_w2", C.c_void_p), ("g_b2", C.c_void_p),
+        ("d_param", C.c_void_p), ("d_m", C.c_void_p), ("d_v", C.c_void_p),
+        ("touched", C.c_void_p), ("touched_list", C.c_void_p), ("n_touched", C.c_void_p), ("gslot", C.c_void_p),
+        ("work", C.c_void_p), ("work_bytes", C.c_int64),
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+    ]
+
+
+RK_AUSH_HG, RK_AUSH_HD = 128, 150
+RK_AUSH_MAX_FILLER, RK_AUSH_MAX_SELECT, RK_AUSH_MAX_PAIRS = 256, 16, 4096
+
 _lib = None
 
 # name -> argtypes (restype is always int unless listed in _RESTYPES)
@@ -178,6 +196,16 @@ _SIGNATURES = {
     "rk_pca_gram": [_I64, _P, _I32, _P, _I32, _P, _P, _P],
     "rk_pca_update": [_I64, _P, _I32, _P, _I32, _P, _P],
     "rk_pca_select": [_I32, _P, _I32, _P, _P],
+    "rk_aush_workspace_bytes": [_I32, _I32, _I32, C.POINTER(_I64)],
+    "rk_aush_eligible": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, C.POINTER(_I32), _P],
+    "rk_aush_permute": [_I32, _P, C.c_uint64, C.c_uint64, _P, _P],
+    "rk_aush_sample": [_I32, _P, _I32, _P, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _I64, _P, _I32, _P, _P, _P, _P, _P],
+    "rk_aush_zr": [_I32, _I32, _I32, _P, C.c_double, C.c_uint64, C.c_uint64, _P, _P],
+    "rk_aush_gen": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
+    "rk_aush_d_step": [C.POINTER(AushDesc), _I32, _P, _P, _P, _P, _P, _P, _I32, _P, _P],
+    "rk_aush_train_epoch": [C.POINTER(AushDesc), _P, _I32, _P, _P, C.c_uint64, C.c_uint64, C.c_double, _I32, _P, _P, _P, _P, _P, _P,
+                            _P, _P, _P],
+    "rk_aush_fake_assemble": [_I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P],
 }
 _RESTYPES = {"rk_last_error": C.c_char_p}
 EXPORTS = tuple(_SIGNATURES)

@@ -14,7 +14,7 @@ from copy import copy
 import numpy as np
 import torch
 
-from .default import DATASET_IMPLICIT
+from .default import DATASET_EXPLICIT, DATASET_IMPLICIT
 from .utils import VarDim, get_logger
 
 
@@ -417,9 +417,301 @@ class ImplicitData:
         pprint({**self.info_describe(), "dataset_name": self.dataset_name})
 
 
-factories = {"implicit": ImplicitData}
+# ---------------------------------------------------------------------------------------------- explicit feedback
+def _coo_to_rating_csr(users, items, ratings, n_rows):
+    """(ptr int64 [n_rows + 1], idx int32, val float32): rows sorted by item, duplicate (user, item) ratings summed --
+    what csr_matrix((rating, (row, col))).toarray() holds (explicit.py:125-134)."""
+    users = np.asarray(users, dtype=np.int64)
+    items = np.asarray(items, dtype=np.int64)
+    ratings = np.asarray(ratings, dtype=np.float32)
+    width = int(items.max()) + 1 if len(items) else 1
+    keys = users * width + items
+    uniq, inv = np.unique(keys, return_inverse=True)
+    val = np.zeros(len(uniq), dtype=np.float32)
+    np.add.at(val, inv, ratings)
+    cnt = np.bincount(uniq // width, minlength=n_rows)[:n_rows] if len(uniq) else np.zeros(n_rows, dtype=np.int64)
+    ptr = np.zeros(n_rows + 1, dtype=np.int64)
+    ptr[1:] = np.cumsum(cnt)
+    return ptr, (uniq % width).astype(np.int32), val
+
+
+def _canonical_rating_csr(csr):
+    """A caller's (ptr, idx, val) with every row sorted by item and duplicates summed (unchanged when it already is)."""
+    ptr, idx, val = (np.asarray(a) for a in csr[:3])
+    ptr = ptr.astype(np.int64)
+    idx = idx.astype(np.int32)
+    val = val.astype(np.float32)
+    if len(idx) != int(ptr[-1]) or len(val) != len(idx):
+        raise ValueError(f"rating CSR sizes disagree: ptr[-1] = {int(ptr[-1])}, {len(idx)} ids, {len(val)} values")
+    n = len(ptr) - 1
+    users = np.repeat(np.arange(n, dtype=np.int64), np.diff(ptr))
+    width = int(idx.max()) + 1 if len(idx) else 1
+    keys = users * width + idx.astype(np.int64)
+    if len(keys) > 1 and not bool(np.all(keys[1:] > keys[:-1])):
+        return _coo_to_rating_csr(users, idx, val, n)
+    return ptr, idx, val
+
+
+def _rows_of(csr, n_rows):
+    ptr, idx, val = csr
+    if len(ptr) - 1 >= n_rows:
+        return ptr[: n_rows + 1], idx[: int(ptr[n_rows])], val[: int(ptr[n_rows])]
+    out = np.full(n_rows + 1, ptr[-1], dtype=np.int64)
+    out[: len(ptr)] = ptr
+    return out, idx, val
+
+
+def _kvr_of(csr):
+    ptr, idx, val = csr
+    users = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
+    return np.column_stack([users.astype(np.float64), idx.astype(np.float64), val.astype(np.float64)])
+
+
+def read_rating_csv(path, header=None, sep=","):
+    """explicit.py:110-120: the columns ['user_id', 'item_id', 'rating'] of a CSV as an [N, 3] array."""
+    import pandas as pd
+
+    header = header if header is not None else ["user_id", "item_id", "rating"]
+    return pd.read_csv(path, engine="python", sep=sep).loc[:, header].to_numpy()
+
+
+class ExplicitData:
+    """Explicit-feedback (rating) dataset: the build's counterpart of recad/dataset/explicit.py.
+
+    Same object contract -- ``info_describe()`` (n_users, n_items, *_interactions, train_kvr, train_mat,
+    batch_describe, user_map after a remap), ``generate_batch(user_filter=)``, ``partial_sample``, ``reset`` -- but the
+    ratings live in CSR arrays (duplicates summed, rows sorted by item).  The reference's dense U x I ``train_mat``
+    (explicit.py:102) is built only on first access and refused above ``dense_limit`` entries; the AUSH attacker never
+    asks for it.  Sources, per split: ``*_csr=(ptr, idx, val)``, the reference's ``*_dict`` [N, 3] (user, item, rating)
+    arrays, or its CSVs (``path_*``).  A missing valid / test split is empty; a missing train split is an error (there
+    is no download)."""
+
+    def __init__(self, **config):
+        self.config = config
+        self.logger = get_logger(f"{__name__}:{self.dataset_name}", level=config["logging_level"])
+        self._mode = "train"
+        self._kvr = {}
+        coo = {}
+        for split in ("train", "valid", "test"):
+            if config.get(f"{split}_csr") is not None:
+                coo[split] = ("csr", _canonical_rating_csr(config[f"{split}_csr"]))
+            elif config.get(f"{split}_dict") is not None:
+                kvr = np.asarray(config[f"{split}_dict"])
+                self._kvr[split] = kvr
+                coo[split] = ("kvr", kvr)
+            elif config.get(f"path_{split}"):
+                kvr = read_rating_csv(config[f"path_{split}"], config["header"], config["sep"])
+                self._kvr[split] = kvr
+                coo[split] = ("kvr", kvr)
+            elif split == "train":
+                raise ValueError(f"ExplicitData({self.dataset_name}): no train split -- give train_csr=(ptr, idx, val), "
+                                 "train_dict=[N, 3] (user, item, rating) rows or path_train=<csv>; there is no download")
+            else:
+                coo[split] = ("kvr", np.zeros((0, 3)))
+                self._kvr[split] = coo[split][1]
+        self.user_map = config.get("user_map")
+        if config["remap_enable"] and self.user_map is None:
+            # explicit.py:71-81: users of the three splits renumbered densely in sorted order
+            ids = [np.repeat(np.arange(len(d[0]) - 1), np.diff(d[0])) if kind == "csr" else d[:, 0].astype(np.int64)
+                   for kind, d in coo.values()]
+            uniq = np.unique(np.concatenate(ids)) if ids else np.zeros(0, dtype=np.int64)
+            self.user_map = {int(u): i for i, u in enumerate(uniq)}
+            remap = np.full(int(uniq.max()) + 1 if len(uniq) else 1, -1, dtype=np.int64)
+            remap[uniq] = np.arange(len(uniq))
+            for split, (kind, d) in list(coo.items()):
+                if kind == "kvr":
+                    d = d.copy()
+                    d[:, 0] = remap[d[:, 0].astype(np.int64)]
+                    self._kvr[split] = d
+                    coo[split] = ("kvr", d)
+                else:
+                    ptr, idx, val = d
+                    users = remap[np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))]
+                    coo[split] = ("csr", _coo_to_rating_csr(users, idx, val, len(uniq)))
+        # n_users / n_items = max id + 1 over train, valid and test (explicit.py:83-100)
+        def extent(kind, d):
+            if kind == "kvr":
+                return ((int(d[:, 0].max()) + 1, int(d[:, 1].max()) + 1) if len(d) else (0, 0))
+            ptr, idx, _ = d
+            rows = np.nonzero(np.diff(ptr))[0]
+            return (int(rows.max()) + 1 if len(rows) else 0, int(idx.max()) + 1 if len(idx) else 0)
+
+        ext = [extent(*v) for v in coo.values()]
+        self.n_users = max(e[0] for e in ext)
+        self.n_items = max(e[1] for e in ext)
+        self._csr = {}
+        sizes = {}
+        for split, (kind, d) in coo.items():
+            if kind == "kvr":
+                self._csr[split] = _coo_to_rating_csr(d[:, 0], d[:, 1], d[:, 2], self.n_users) if len(d) else \
+                    (np.zeros(self.n_users + 1, dtype=np.int64), np.zeros(0, dtype=np.int32), np.zeros(0, dtype=np.float32))
+                sizes[split] = len(d)
+            else:
+                self._csr[split] = _rows_of(d, self.n_users)
+                sizes[split] = int(self._csr[split][0][-1])
+        self.train_size, self.valid_size, self.test_size = sizes["train"], sizes["valid"], sizes["test"]
+        self._train_mat = None
+
+    # ------------------------------------------------------------------ construction
+    @classmethod
+    def from_config(cls, name, **user_config):
+        config = {k: copy(v) for k, v in DATASET_EXPLICIT.items()}
+        for k, v in user_config.items():
+            if k == "download":
+                continue
+            if k not in config:
+                get_logger(__name__).debug(f"Unexpected key [{k}] for {cls}")
+            config[k] = v
+        inst = object.__new__(cls)
+        inst._dataset_name = name
+        inst._init_config = config
+        inst.__init__(**config)
+        return inst
+
+    @property
+    def dataset_name(self):
+        return getattr(self, "_dataset_name", type(self).__name__)
+
+    def reset(self, **kwargs):
+        config = copy(self._init_config)
+        for k, v in kwargs.items():
+            if k not in config:
+                raise ValueError(f"reset arg {k} should be in {list(config)}")
+            config[k] = v
+            if k.endswith("_dict") and v is not None:
+                config[k.replace("_dict", "_csr")] = None
+            if k.endswith("_csr") and v is not None:
+                config[k.replace("_csr", "_dict")] = None
+        return type(self).from_config(self.dataset_name, **config)
+
+    # ------------------------------------------------------------------ description
+    def rating_csr(self, split="train"):
+        """(ptr int64 [n_users + 1], idx int32, val float32) of a split: rows sorted by item, duplicates summed."""
+        return self._csr[split]
+
+    @property
+    def train_kvr(self):
+        if "train" not in self._kvr:
+            self._kvr["train"] = _kvr_of(self._csr["train"])
+        return self._kvr["train"]
+
+    @property
+    def train_mat(self):
+        """The dense U x I float32 rating array of the reference (explicit.py:102), built on first access."""
+        if self._train_mat is None:
+            n = self.n_users * self.n_items
+            if n > self.config["dense_limit"]:
+                raise MemoryError(f"ExplicitData.train_mat: a dense {self.n_users} x {self.n_items} array ({n * 4 / 2 ** 30:.1f} GiB) "
+                                  f"is above dense_limit = {self.config['dense_limit']} entries; use rating_csr() instead")
+            ptr, idx, val = self._csr["train"]
+            mat = np.zeros((self.n_users, self.n_items), dtype=np.float32)
+            mat[np.repeat(np.arange(self.n_users), np.diff(ptr)), idx] = val
+            self._train_mat = mat
+        return self._train_mat
+
+    def batch_describe(self):
+        if self._mode == "train":
+            b = VarDim(max=self.config["batch_size"], comment="batch size")
+            return {"users": (torch.int64, b), "users_mat": (torch.float32, (b, self.n_items))}
+
+    class _Info(dict):
+        """info_describe() result; train_kvr / train_mat are materialised on first access."""
+
+        def __init__(self, ds, base):
+            super().__init__(base)
+            self._ds = ds
+
+        def __missing__(self, key):
+            if key not in ("train_kvr", "train_mat"):
+                raise KeyError(key)
+            self[key] = getattr(self._ds, key)
+            return self[key]
+
+        def get(self, key, default=None):
+            try:
+                return self[key]
+            except KeyError:
+                return default
+
+        def keys(self):
+            return list(super().keys()) + [k for k in ("train_kvr", "train_mat") if not dict.__contains__(self, k)]
+
+        def __contains__(self, key):
+            return dict.__contains__(self, key) or key in ("train_kvr", "train_mat")
+
+    def info_describe(self):
+        base = {"n_users": self.n_users, "n_items": self.n_items, "train_interactions": self.train_size,
+                "valid_interactions": self.valid_size, "test_interactions": self.test_size,
+                "batch_describe": self.batch_describe()}
+        if self.user_map is not None:
+            base["user_map"] = self.user_map
+        return ExplicitData._Info(self, base)
+
+    def mode(self):
+        return self._mode
+
+    def switch_mode(self, mode):
+        assert mode in ["train", "test", "validate"]
+        self._mode = mode
+
+    def _dense_rows(self, users):
+        ptr, idx, val = self._csr["train"]
+        out = np.zeros((len(users), self.n_items), dtype=np.float32)
+        for r, u in enumerate(users):
+            out[r, idx[ptr[u]:ptr[u + 1]]] = val[ptr[u]:ptr[u + 1]]
+        return out
+
+    def generate_batch(self, **config):
+        """explicit.py:178-199: a permutation (np.random) of the users user_filter(train_mat=...) returns (all users without
+        a filter) in batches of batch_size, each with its dense rating rows."""
+        if self._mode != "train":
+            return
+        user_filter = config.get("user_filter", None)
+        bs = self.config["batch_size"]
+        avail = user_filter(train_mat=self.train_mat) if user_filter is not None else list(range(self.n_users))
+        avail = np.random.permutation(avail)
+        dev = self.config["device"]
+        for b in range((len(avail) + bs - 1) // bs):
+            users = avail[b * bs:(b + 1) * bs]
+            yield {"users": torch.tensor(users, dtype=torch.int64).to(dev),
+                   "users_mat": torch.tensor(self._dense_rows(users), dtype=torch.float32).to(dev)}
+
+    def inject_data(self, mode, data, **kwargs):
+        raise NotImplementedError("ExplicitData.inject_data: not supported (the reference's explicit dataset has none either)")
+
+    def delete_data(self, mode, user_id, data, **kwargs):
+        raise NotImplementedError("ExplicitData.delete_data: not supported (the reference's explicit dataset has none either)")
+
+    def partial_sample(self, **kwargs):
+        """explicit.py:210-240: np.random.shuffle the unique train users, keep int(len * user_ratio) of them in every split
+        and renumber them densely in sorted order (user_map); item ids are kept, so n_items may shrink."""
+        assert "user_ratio" in kwargs, "Expect to have [user_ratio]"
+        ratio = kwargs["user_ratio"]
+        ptr = self._csr["train"][0]
+        users = np.nonzero(np.diff(ptr))[0]
+        np.random.shuffle(users)
+        left = np.sort(users[: int(len(users) * ratio)])
+        new_map = {int(u): k for k, u in enumerate(left.tolist())}
+        splits = {}
+        for split in ("train", "valid", "test"):
+            p, i, v = self._csr[split]
+            cnt = np.diff(p)[left]
+            np_ = np.zeros(len(left) + 1, dtype=np.int64)
+            np_[1:] = np.cumsum(cnt)
+            sel = np.concatenate([np.arange(p[u], p[u + 1]) for u in left]) if len(left) else np.zeros(0, dtype=np.int64)
+            splits[split] = (np_, i[sel], v[sel])
+        return self.reset(train_csr=splits["train"], valid_csr=splits["valid"], test_csr=splits["test"], remap_enable=True,
+                          user_map=new_map, if_cache=False)
+
+    def print_help(self, **kwargs):
+        from pprint import pprint
+
+        pprint({**self.info_describe(), "dataset_name": self.dataset_name})
+
+
+factories = {"implicit": ImplicitData, "explicit": ExplicitData}
 
 
 def from_config(scope, *args, **kwargs):
-    """dataset.from_config("implicit", name, **kw) (recad/dataset/__init__.py:13-17)."""
+    """dataset.from_config("implicit" | "explicit", name, **kw) (recad/dataset/__init__.py:13-17)."""
     return factories[scope].from_config(*args, **kwargs)

@@ -1,8 +1,8 @@
 """Default configuration registry for the victim path.
 
-Mirrors the keys and values of the reference's registry for the three victims and the
-PCASelectUsers defender (recad/default.py:103-132,223-228) and the implicit dataset / workflow knobs the hot path reads
-(recad/default.py:49-62,247-267).  Only what the path needs is present.
+Mirrors the keys and values of the reference's registry for the three victims, the random and AUSH attackers, the
+PCASelectUsers defender (recad/default.py:103-168,223-228) and the implicit / explicit dataset and workflow knobs the
+hot path reads (recad/default.py:49-99,247-267).  Only what the path needs is present.
 """
 import logging
 import os
@@ -24,7 +24,12 @@ MODEL = {
             "optim": "adam", "lr": 1e-3,
         },
     },
-    "attacker": {"random": {"attack_num": 50, "filler_num": 36}},
+    "attacker": {
+        "random": {"attack_num": 50, "filler_num": 36},
+        # recad/default.py:159-168; seed is this build's: the key of the device RNG (None = drawn from np.random at .I())
+        "aush": {"attack_num": 50, "filler_num": 36, "lr_g": 0.01, "lr_d": 0.001, "optim_g": "adam", "optim_d": "adam",
+                 "selected_ids": [62], "ZR_ratio": 0.2, "seed": None},
+    },
     # recad/default.py:223-228; block / tol / max_iter / seed are this build's solver knobs (block None = 8, or 16 when kVals > 5)
     "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED}},
 }
@@ -43,6 +48,18 @@ DATASET_IMPLICIT = {
     # build-specific (no reference counterpart):
     "graph_source": "reference",  # "reference" = adjacency/positives from the LAST split read (test); "train"
     "sampler": "auto",            # "numpy" (vectorised host) | "device" (HIP) | "auto" = device when on a GPU
+}
+
+# recad/default.py:67-89 (the "explicit" scope) and the keys _decorate_config adds (:92-99)
+DATASET_EXPLICIT = {
+    "path_train": None, "path_test": None, "path_valid": None,
+    "batch_size": 256, "header": None, "sep": ",", "threshold": 4, "sample": "row",
+    "logging_level": logging.INFO, "train_dict": None, "valid_dict": None, "test_dict": None, "remap_enable": False,
+    "device": DEVICE, "if_cache": False, "cache_dir": os.path.join(".", "generated"),
+    # build-specific (no reference counterpart):
+    "train_csr": None, "valid_csr": None, "test_csr": None,   # (ptr, idx, val) rating CSRs
+    "user_map": None,             # set by partial_sample: the remap it applied
+    "dense_limit": 1 << 28,       # train_mat (dense U x I float32) is refused above this many entries (1 GiB)
 }
 
 WORKFLOW = {
@@ -65,6 +82,7 @@ def set_device_id(cuda_id):
         for cfg in scope.values():
             cfg["device"] = device
     DATASET_IMPLICIT["device"] = device
+    DATASET_EXPLICIT["device"] = device
     for cfg in WORKFLOW.values():
         cfg["device"] = device
     return device

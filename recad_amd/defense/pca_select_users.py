@@ -52,7 +52,14 @@ def sign_fix(vecs):
 def rating_csr(dataset, device):
     """The defender's U x I rating matrix as a device CSR: (U, I, rowptr int32, col int32, val float32).
     Accepts an ImplicitData (its train CSR, every value 1.0), a rating CSR tuple (ptr, idx, val[, n_items]),
-    a dense U x I array (the reference's users_mat rows), or an object whose info_describe() has "train_mat"."""
+    a dense U x I array (the reference's users_mat rows), or an object whose info_describe() has "train_mat".
+    An ExplicitData gives its train rating CSR, values as they are (the reference's defense_data, explicit.py:102)."""
+    from ..dataset import ExplicitData
+
+    if isinstance(dataset, ExplicitData):
+        ptr, idx, val = dataset.rating_csr("train")
+        return (int(dataset.n_users), int(dataset.n_items), torch.as_tensor(ptr.astype(np.int32)).to(device),
+                torch.as_tensor(idx.astype(np.int32)).to(device), torch.as_tensor(val.astype(np.float32)).to(device))
     if hasattr(dataset, "train_csr_sorted") and hasattr(dataset, "n_items"):
         ptr, idx = dataset.train_csr_sorted()
         U, I = int(dataset.n_users), int(dataset.n_items)

@@ -1,8 +1,9 @@
-"""model.from_config("victim" | "defender", name, **kw): the reference's factory (recad/model/__init__.py:3-21)
-for the victims and the defender this build implements."""
-from . import defense, victim
+"""model.from_config("victim" | "attacker" | "defender", name, **kw): the reference's factory (recad/model/__init__.py:3-21)
+for the victims, attackers and defender this build implements."""
+from . import attack, defense, victim
 
 factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": victim.NCF},
+             "attacker": {"aush": attack.Aush, "random": attack.RandomAttacker},
              "defender": {"PCASelectUsers": defense.PCASelectUsers}}
 
 

@@ -134,3 +134,19 @@ def make_device(name, device):
         p[1:] = torch.cumsum(c, 0)
         out[key] = (p, items[m].contiguous())
     return out
+
+
+def with_ratings(data, seed=None):
+    """Explicit-feedback data on the same shapes: every interaction of `make(name)` (or of a dict it returned) gets a seeded
+    1..5 rating (a rounded N(3.6, 1.1), clipped -- the rating moments of the random attack).  Returns the dict with
+    train / valid / test as (ptr int64, idx int32, val float32) rating CSRs: ExplicitData's train_csr= / valid_csr= /
+    test_csr= inputs.  The implicit generators are not changed."""
+    d = make(data) if isinstance(data, str) else dict(data)
+    rng = np.random.default_rng(SHAPES[d["name"]][5] + 7 if seed is None else seed)
+    out = dict(d)
+    for split in ("train", "valid", "test"):
+        ptr, idx = d[split]
+        ptr, idx = np.asarray(ptr), np.asarray(idx)
+        val = np.clip(np.round(rng.normal(3.6, 1.1, len(idx))), 1, 5).astype(np.float32)
+        out[split] = (ptr, idx, val)
+    return out
