@@ -591,6 +591,49 @@ int rk_aush_fake_assemble(int32_t n_rows, int32_t n_items, int32_t filler_num, c
                           const int32_t *sel, int32_t n_sel, const float *gen, const int32_t *tgt, int32_t n_tgt, float *pre, float *out,
                           void *stream);
 
+/* AIA (recad/model/attacker/aia.py, registry recad/default.py:169-186): the weighted-MF surrogate trained from scratch on every
+ * train_step, the reverse pass through its unrolled Adam steps, the attack loss and the generator's Adam step.  The surrogate's
+ * data is one CSR of R = n_real + fake rows (the rating CSR, then filler_num slots per fake row holding the projected generator),
+ * item ids ascending inside a row; weight_neg_s is 0, so an entry weighs w_pos when X > 0 and nothing otherwise.  Its state
+ * is [P (R rows); Q (n_items rows)], each row dpad floats (d padded with zero columns); a SLOT is theta, m, v of that shape,
+ * 3 (R + n_items) dpad floats.  Step j of an epoch trains the rows perm[j * batch .. min((j + 1) * batch, R)).  recad_amd/attack/
+ * aia.py drives these entries; all pointers are device pointers and calls are asynchronous on `stream`.  No float atomics:
+ * every result is bit-reproducible. */
+#define RK_AIA_MAX_BATCH 256      /* batch_size_s limit */
+
+typedef struct rk_aia_desc {
+    int32_t n_rows, n_real, n_items, dpad, batch, n_fake_nz;
+    int64_t nnz_real;              /* the fake rows' entries start here in col / x */
+    const int32_t *rowptr, *col;   /* [n_rows + 1] / [nnz_real + n_fake_nz] */
+    const float *x;                /* [nnz_real + n_fake_nz]: ratings, then the projected generator (rk_aia_project) */
+    float lr, beta1, beta2, eps, wd, w_pos;   /* the surrogate's torch.optim.Adam(lr_s, weight_decay=weight_decay_s), weight_pos_s */
+} rk_aia_desc;
+
+/* x[k] = clamp(round_half_even(gen[k]), 0, 5) (project, aia.py:534-549). */
+int rk_aia_project(int32_t n, const float *gen, float *x, void *stream);
+/* Steps lo .. hi-1 of one epoch of the surrogate (aia.py:444-461), Adam steps adam_t_lo, adam_t_lo + 1, ...: batch loss
+ * sum_r sum_i w (X_ri - p_r . q_i)^2 over the batch's positives, weight decay on every row, one launch per step.  keep_all:
+ * step lo + k reads slot k of `slots` and writes slot k + 1 (hi - lo + 1 slots); otherwise two slots, step lo + k reads slot
+ * (parity0 + k) & 1 and writes the other. */
+int rk_aia_forward(const rk_aia_desc *desc, const int32_t *perm, const int32_t *invperm, int32_t lo, int32_t hi, int32_t adam_t_lo,
+                   float *slots, int32_t keep_all, int32_t parity0, void *stream);
+/* The reverse of steps hi-1 down to lo (the unrolled epoch, aia.py:463-482): slots as rk_aia_forward's keep_all (slot k = the
+ * input of step lo + k).  adj [3 slots' worth: theta-bar, m-bar, v-bar] is updated in place from the adjoint of step hi's
+ * output to that of step lo's input; gbar [(R + n_items) dpad] is scratch; xbar [n_fake_nz] accumulates dF/dX of the fake
+ * entries (zero it before the first call).  Where v' == 0 exactly, the 1 / sqrt(v') term of v-bar is taken as 0. */
+int rk_aia_reverse(const rk_aia_desc *desc, const int32_t *perm, const int32_t *invperm, int32_t lo, int32_t hi, int32_t adam_t_lo,
+                   const float *slots, float *adj, float *gbar, float *xbar, void *stream);
+/* G_loss (aia.py:88-114) of theta = P Q^T into loss[0] and its gradient into adj (zeroed first; P rows of real users and Q rows
+ * set, m-bar / v-bar zero).  Pairs (user, target) with train_mat[u, t] == 0, grouped by target: pair_ptr [n_tgt + 1],
+ * pair_user / pair_tgt (item id) / pair_slot (target index) [n_pairs]; pidx [n_tgt, n_real] = the pair index or -1; tscale
+ * [n_tgt] = 1 / (11 |T_t|) (as float).  work: 3 n_pairs floats. */
+int rk_aia_attack_loss(const rk_aia_desc *desc, int32_t n_tgt, const int32_t *tgt, const int32_t *pair_ptr, int32_t n_pairs,
+                       const int32_t *pair_user, const int32_t *pair_tgt, const int32_t *pair_slot, const int32_t *pidx,
+                       const float *tscale, const float *theta, float *work, float *loss, float *adj, void *stream);
+/* torch.optim.Adam step adam_t (no weight decay) on gen [n] with gradient grad: the G optimizer (aia.py:22-37, 66-68). */
+int rk_aia_g_step(int32_t n, float *gen, float *m, float *v, const float *grad, int32_t adam_t, float lr, float beta1, float beta2,
+                  float eps, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -130,6 +130,18 @@ class AushDesc(C.Structure):
     ]
 
 
+class AiaDesc(C.Structure):
+    """rk_aia_desc (include/recad_hip.h)."""
+
+    _fields_ = [
+        ("n_rows", C.c_int32), ("n_real", C.c_int32), ("n_items", C.c_int32), ("dpad", C.c_int32), ("batch", C.c_int32),
+        ("n_fake_nz", C.c_int32), ("nnz_real", C.c_int64),
+        ("rowptr", C.c_void_p), ("col", C.c_void_p), ("x", C.c_void_p),
+        ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("wd", C.c_float), ("w_pos", C.c_float),
+    ]
+
+
+RK_AIA_MAX_BATCH = 256
 RK_AUSH_HG, RK_AUSH_HD = 128, 150
 RK_AUSH_MAX_FILLER, RK_AUSH_MAX_SELECT, RK_AUSH_MAX_PAIRS = 256, 16, 4096
 
@@ -206,6 +218,11 @@ _SIGNATURES = {
     "rk_aush_train_epoch": [C.POINTER(AushDesc), _P, _I32, _P, _P, C.c_uint64, C.c_uint64, C.c_double, _I32, _P, _P, _P, _P, _P, _P,
                             _P, _P, _P],
     "rk_aush_fake_assemble": [_I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P],
+    "rk_aia_project": [_I32, _P, _P, _P],
+    "rk_aia_forward": [C.POINTER(AiaDesc), _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P],
+    "rk_aia_reverse": [C.POINTER(AiaDesc), _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P],
+    "rk_aia_attack_loss": [C.POINTER(AiaDesc), _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rk_aia_g_step": [_I32, _P, _P, _P, _P, _I32, _F, _F, _F, _F, _P],
 }
 _RESTYPES = {"rk_last_error": C.c_char_p}
 EXPORTS = tuple(_SIGNATURES)

@@ -1,3 +1,4 @@
+from .aia import AIA
 from .aush import Aush, RandomAttacker
 
-__all__ = ["Aush", "RandomAttacker"]
+__all__ = ["AIA", "Aush", "RandomAttacker"]

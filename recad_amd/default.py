@@ -1,7 +1,7 @@
 """Default configuration registry for the victim path.
 
-Mirrors the keys and values of the reference's registry for the three victims, the random and AUSH attackers, the
-PCASelectUsers defender (recad/default.py:103-168,223-228) and the implicit / explicit dataset and workflow knobs the
+Mirrors the keys and values of the reference's registry for the three victims, the random, AUSH and AIA attackers,
+the PCASelectUsers defender (recad/default.py:103-186,223-228) and the implicit / explicit dataset and workflow knobs the
 hot path reads (recad/default.py:49-99,247-267).  Only what the path needs is present.
 """
 import logging
@@ -29,6 +29,12 @@ MODEL = {
         # recad/default.py:159-168; seed is this build's: the key of the device RNG (None = drawn from np.random at .I())
         "aush": {"attack_num": 50, "filler_num": 36, "lr_g": 0.01, "lr_d": 0.001, "optim_g": "adam", "optim_d": "adam",
                  "selected_ids": [62], "ZR_ratio": 0.2, "seed": None},
+        # recad/default.py:169-186; history_bytes is this build's: the cap of the unrolled epochs' stored states (theta, m, v per
+        # step); above it the reverse pass keeps a checkpoint every ceil(sqrt(K)) steps and re-runs each segment forward
+        "aia": {"attack_num": 50, "filler_num": 36, "lr_g": 0.01, "lr_d": 0.001, "optim_g": "adam", "optim_d": "adam",
+                "surrogate_model": "WMF", "epoch_s": 50, "unroll_steps_s": 1, "hidden_dim_s": 16, "lr_s": 1e-2,
+                "weight_decay_s": 1e-5, "batch_size_s": 16, "weight_pos_s": 1.0, "weight_neg_s": 0.0, "selected_ids": [62],
+                "history_bytes": 1 << 30},
     },
     # recad/default.py:223-228; block / tol / max_iter / seed are this build's solver knobs (block None = 8, or 16 when kVals > 5)
     "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED}},
