@@ -36,6 +36,17 @@ def effective_k(k, n_users, n_items):
     return 3 if k >= min(n_users, n_items) else int(k)
 
 
+def block_width(k):
+    """Width b of the iteration block for k wanted eigenpairs: 8 up to k = 3, 16 from k = 4 to 16.  The b - k guard vectors set
+    the convergence rate lambda_{b+1} / lambda_k; with b = 8, k = 5 leaves three guards and the reference's dev data (lambda_5
+    and lambda_6 0.14 % apart, lambda_9 / lambda_5 = 0.977) does not reach tol in 300 iterations, k = 4 needs 240 of them
+    (DESIGN.md section 9).  k = 3 keeps the width it has always had.  Above 16 no supported width holds k."""
+    k = int(k)
+    if k < 1 or k > 16:
+        raise ValueError(f"kVals = {k}: the solver's block holds 1 to 16 eigenpairs (block width 8 or 16)")
+    return 8 if k <= 3 else 16
+
+
 def sign_fix(vecs):
     """The sign convention: column j is negated unless its entry of largest |value| (lowest index on a tie) is positive.
     numpy (host) or torch (any device) arrays of shape [n, k]."""
@@ -169,8 +180,8 @@ def subspace_eigs(op, k, b, tol=1e-5, max_iter=300, seed=2023):
     Returns (eigenvalues float64 [k] descending, eigenvectors fp32 device [I, k] (sign convention applied), iterations,
     residuals)."""
     n, dev = op.I, op.val.device
-    if b not in (8, 16) or k > b:
-        raise ValueError(f"block width {b} must be 8 or 16 and at least k = {k}")
+    if b not in (8, 16) or k > b or k < 1:
+        raise ValueError(f"block width {b} (key `block`) must be 8 or 16 and at least kVals = {k} >= 1")
     if n < b:
         raise ValueError(f"{n} items: fewer than the block width {b}")
     blk = _Block(n, dev)
@@ -186,8 +197,13 @@ def subspace_eigs(op, k, b, tol=1e-5, max_iter=300, seed=2023):
         VV, VW, WW = G[:b, :b], G[:b, b:], G[b:, b:]
         H = 0.5 * (VW + VW.T)
         # generalised Ritz problem H q = lam VV q (VV = I up to fp32 rounding of V)
-        Lc = np.linalg.cholesky(VV)
-        Li = np.linalg.inv(Lc)
+        try:
+            Li = np.linalg.inv(np.linalg.cholesky(VV))
+        except np.linalg.LinAlgError as e:
+            # CholQR2 leaves V orthonormal to fp32 rounding whenever its input had b independent columns: this can fail only
+            # when C has numerically fewer than b nonzero eigenvalues
+            raise RuntimeError(f"PCASelectUsers: the iteration block lost rank in iteration {it} (block {b}, k {k}): the scaled "
+                               f"rating matrix has fewer than {b} independent columns") from e
         lam_all, Z = np.linalg.eigh(Li @ H @ Li.T)
         order = np.argsort(-lam_all, kind="stable")
         lam_all, Q = lam_all[order], (Li.T @ Z)[:, order]
@@ -267,7 +283,7 @@ class PCASelectUsers(BaseVictim):
         k = effective_k(self.kVals, U, I)
         if k != self.kVals:
             self.logger.info(f"k-vals is more than the number of user or item, so it is set to {k}")
-        b = int(self.block) if self.block else (16 if k > 5 else 8)
+        b = int(self.block) if self.block else block_width(k)
         op = CovarianceOperator(U, I, rowptr, col, val)
         self.k = k
         self.eigenvalues, self.eigenvectors, self.iterations, self.residuals = subspace_eigs(

@@ -1,5 +1,6 @@
 """CPU tests of the PCASelectUsers defender (recad_amd/defense): the reference's counting rules, the sign
-convention, the registry / lazy-init contract, the workflow hook and the golden fixture's own consistency."""
+convention, the registry / lazy-init contract, the workflow hook, the golden fixture's own consistency, and the block-width
+rule against a numpy restatement of the solver (tests/_pca_restate.py)."""
 import os
 
 import numpy as np
@@ -7,7 +8,7 @@ import pytest
 import torch
 
 from recad_amd import _lib, dataset, default, model, synth, workflow
-from recad_amd.defense.pca_select_users import effective_k, flag_count, sign_fix
+from recad_amd.defense.pca_select_users import block_width, effective_k, flag_count, sign_fix
 from recad_amd.utils import NotInstantiatedError
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -132,3 +133,44 @@ def test_golden_fixture_is_consistent(name):
     m = flag_count(int(g["attack_num"]), U)
     assert len(g["spam"]) == len(g["spam_conv"]) == m
     assert g["spam_conv"].tolist() == np.argsort(g["dist_conv"], kind="stable")[:m].tolist()
+
+
+def test_block_width_rule():
+    assert [block_width(k) for k in (1, 2, 3)] == [8, 8, 8], "kVals <= 3 keeps the 8-wide block its fixtures were recorded with"
+    assert all(block_width(k) == 16 for k in range(4, 17))
+    for k in (0, 17, 100):
+        with pytest.raises(ValueError, match="kVals"):
+            block_width(k)
+    assert default.MODEL["defender"]["PCASelectUsers"]["block"] is None, "the default configuration uses the rule"
+
+
+_RESTATED = [("pca_dev_kreset", k) for k in range(1, 17)] + [("pca_game_fake50", k) for k in (3, 8, 15, 16)]
+
+
+@pytest.mark.parametrize("name,k", _RESTATED)
+def test_block_width_converges_in_the_restatement(name, k):
+    """The width block_width(k) picks reaches the default tol within the default max_iter on both stored matrices, in the numpy
+    restatement of subspace_eigs (fp64 arithmetic, V / T / W rounded to fp32).  dev at every kVals (it is small, and the slowest:
+    203 and 211 iterations at 15 and 16, 165 at 3), game at the two slowest (121 and 230 at 15 and 16) and two easy ones."""
+    from tests._pca_restate import golden_operator, subspace_eigs_restated
+
+    cfg = default.MODEL["defender"]["PCASelectUsers"]
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    apply, U, I = golden_operator(g)
+    assert effective_k(k, U, I) == k
+    lam, it, res = subspace_eigs_restated(apply, I, k, block_width(k), tol=cfg["tol"], max_iter=cfg["max_iter"], seed=cfg["seed"])
+    assert it is not None, f"{name} kVals {k} block {block_width(k)}: residuals / lambda_1 {res} after {cfg['max_iter']} iterations"
+    assert np.allclose(lam[: min(k, 3)], g["vals_conv"][: min(k, 3)], rtol=1e-4), "the restatement solves the fixture's problem"
+
+
+def test_eight_wide_block_stalls_at_k5_in_the_restatement():
+    """Why the rule switches to 16 at kVals = 4 and not at 6: with three guard vectors dev's fifth eigenpair (lambda_5 / lambda_6
+    = 1.0014, lambda_9 / lambda_5 = 0.977) is still at 4e-4 * lambda_1 after 300 iterations, and kVals = 4 needs 241 of them."""
+    from tests._pca_restate import golden_operator, subspace_eigs_restated
+
+    apply, U, I = golden_operator(np.load(os.path.join(GOLDEN, "pca_dev_kreset.npz")))
+    _, it, res = subspace_eigs_restated(apply, I, 5, 8)
+    assert it is None and res.max() > 1e-4, (it, res)
+    _, it4, _ = subspace_eigs_restated(apply, I, 4, 8)
+    _, it16, _ = subspace_eigs_restated(apply, I, 5, 16)
+    assert it4 is not None and it4 > 200 and it16 is not None and it16 < 60, (it4, it16)
