@@ -634,6 +634,49 @@ int rk_aia_attack_loss(const rk_aia_desc *desc, int32_t n_tgt, const int32_t *tg
 int rk_aia_g_step(int32_t n, float *gen, float *m, float *v, const float *grad, int32_t adam_t, float lr, float beta1, float beta2,
                   float eps, void *stream);
 
+/* AushPlus (recad/model/attacker/aushplus.py, registry recad/default.py:187-209): the discretising autoencoder generator
+ * DiscretGenerator_AE_1(p_dims = [n_items, 125]) and the Discriminator (n_items -> 512 -> 128 -> 1), on CSR rows only: every
+ * consumer of the generator reads it where the input row is non-zero, so nothing rows x n_items is formed.  recad_amd/attack/
+ * aushplus.py drives these entries (and rk_aia_* for the surrogate, rk_adam_step for the optimisers).  No float atomics.
+ * Packed generator parameters (and gradients), float32:
+ *   w1t [n_items, RK_AP_HG] (layers.0.weight transposed, hidden 125 padded with zeros) | b1 [RK_AP_HG] | w2 [n_items, RK_AP_HG]
+ *   (layers.1.weight, padded) | b2 [n_items] | min_boundary_value [n_items] | interval_lengths [n_items, 3]
+ * Packed discriminator parameters (and gradients):
+ *   w1t [n_items, RK_AP_HD1] (main.0.weight transposed) | b1 [RK_AP_HD1] | W2 [RK_AP_HD2, RK_AP_HD1] | b2 [RK_AP_HD2] | w3 [RK_AP_HD2] | b3 [1] */
+#define RK_AP_HG 128
+#define RK_AP_HG_REAL 125
+#define RK_AP_HD1 512
+#define RK_AP_HD2 128
+#define RK_AP_G_FLOATS(I) ((int64_t)(I) * (2 * RK_AP_HG + 5) + RK_AP_HG)
+#define RK_AP_D_FLOATS(I) ((int64_t)(I) * RK_AP_HD1 + RK_AP_HD1 + (int64_t)RK_AP_HD2 * RK_AP_HD1 + 2 * RK_AP_HD2 + 1)
+/* floats of rk_ap_d_step's work per row: h1, dz1 [RK_AP_HD1 each], h2, dz2 [RK_AP_HD2 each], p, dlogit, weighted row loss; stored
+ * array by array over the n rows in that order */
+#define RK_AP_D_WORK_PER_ROW (2 * RK_AP_HD1 + 2 * RK_AP_HD2 + 3)
+
+/* Generator forward (aushplus.py:425-447, 311-378) over rows rowptr[0 .. n_rows] of a CSR (rowptr holds offsets into col / x and
+ * into the per-entry outputs): norm [n_rows] = max(||x_r||, 1e-12), h1 [n_rows, RK_AP_HG] = relu(W1 x_r / norm + b1), and per
+ * stored entry k = (r, j): a = 2.5 tanh(W2_j . h1 + b2_j) + 2.5, cls = the class c in 0..4 whose four Heaviside factors all
+ * hold (-1 when a sits exactly on a boundary: the all-zero distribution), value = (cls + 1) [x > 0]. */
+int rk_ap_g_forward(int32_t n_rows, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *x, const float *gparam,
+                    float *norm, float *h1, float *a, int32_t *cls, float *value, void *stream);
+/* Generator backward into ggrad (packed; every element written).  mode 0: from dvalue = dL/dvalue per entry (taken where
+ * x > 0); mode 1: from CrossEntropyLoss of the five 0/1 products against x - 1 over the entries with x > 0, scale = 1 / their
+ * number, loss[0] = that mean.  The Heaviside's backward is dy (1 - tanh^2) (HeaviTanh, aushplus.py:192-224).  tptr [n_items + 1],
+ * tent, trow: the rows' entries grouped by item in a fixed order (entry index into col / x, row index relative to rowptr).
+ * Scratch: zbar, eloss [per entry, indexed like col], bbar [4 per entry], dpre [n_rows, RK_AP_HG]; entry0 = rowptr[0] and
+ * n_entries = rowptr[n_rows] - rowptr[0] as the host knows them (mode 1 sums eloss over that range in a fixed order). */
+int rk_ap_g_backward(int32_t n_rows, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *x, const float *gparam,
+                     const float *norm, const float *h1, const float *a, int32_t mode, const float *dvalue, float scale,
+                     int64_t entry0, int64_t n_entries, const int32_t *tptr, const int32_t *tent, const int32_t *trow, float *zbar, float *bbar,
+                     float *eloss, float *dpre, float *ggrad, float *loss, void *stream);
+/* Discriminator forward, nn.BCELoss and backward (aushplus.py:103-131, 57-60) on nA rows of CSR A (label labelA) followed by nB
+ * rows of CSR B (labelB): loss[0] = mean_A BCE + mean_B BCE.  dgrad (optional, packed, every element written) needs the
+ * entries of all n = nA + nB rows grouped by item: tptr [n_items + 1], trow (row in 0..n), tsrc (index into valA for an A row,
+ * into valB for a B row).  dinB (optional) receives dL/dvalB at B's entries.  work: n * RK_AP_D_WORK_PER_ROW floats. */
+int rk_ap_d_step(int32_t n_items, int32_t nA, const int32_t *rowptrA, const int32_t *colA, const float *valA, float labelA, int32_t nB,
+                 const int32_t *rowptrB, const int32_t *colB, const float *valB, float labelB, const float *dparam, float *work,
+                 const int32_t *tptr, const int32_t *trow, const int32_t *tsrc, float *dgrad, float *dinB, float *loss, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,6 +144,8 @@ class AiaDesc(C.Structure):
 RK_AIA_MAX_BATCH = 256
 RK_AUSH_HG, RK_AUSH_HD = 128, 150
 RK_AUSH_MAX_FILLER, RK_AUSH_MAX_SELECT, RK_AUSH_MAX_PAIRS = 256, 16, 4096
+RK_AP_HG, RK_AP_HG_REAL, RK_AP_HD1, RK_AP_HD2 = 128, 125, 512, 128
+RK_AP_D_WORK_PER_ROW = 2 * RK_AP_HD1 + 2 * RK_AP_HD2 + 3
 
 _lib = None
 
@@ -223,6 +225,9 @@ _SIGNATURES = {
     "rk_aia_reverse": [C.POINTER(AiaDesc), _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P],
     "rk_aia_attack_loss": [C.POINTER(AiaDesc), _I32, _P, _P, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "rk_aia_g_step": [_I32, _P, _P, _P, _P, _I32, _F, _F, _F, _F, _P],
+    "rk_ap_g_forward": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rk_ap_g_backward": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _P, _F, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rk_ap_d_step": [_I32, _I32, _P, _P, _P, _F, _I32, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P, _P],
 }
 _RESTYPES = {"rk_last_error": C.c_char_p}
 EXPORTS = tuple(_SIGNATURES)

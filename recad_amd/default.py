@@ -1,7 +1,7 @@
 """Default configuration registry for the victim path.
 
-Mirrors the keys and values of the reference's registry for the three victims, the random, AUSH and AIA attackers,
-the PCASelectUsers defender (recad/default.py:103-186,223-228) and the implicit / explicit dataset and workflow knobs the
+Mirrors the keys and values of the reference's registry for the three victims, the random, AUSH, AIA and AushPlus attackers,
+the PCASelectUsers defender (recad/default.py:103-209,223-228) and the implicit / explicit dataset and workflow knobs the
 hot path reads (recad/default.py:49-99,247-267).  Only what the path needs is present.
 """
 import logging
@@ -35,6 +35,12 @@ MODEL = {
                 "surrogate_model": "WMF", "epoch_s": 50, "unroll_steps_s": 1, "hidden_dim_s": 16, "lr_s": 1e-2,
                 "weight_decay_s": 1e-5, "batch_size_s": 16, "weight_pos_s": 1.0, "weight_neg_s": 0.0, "selected_ids": [62],
                 "history_bytes": 1 << 30},
+        # recad/default.py:187-209 (pretrain_epoch_d is there and never read); history_bytes as for aia
+        "aushplus": {"attack_num": 50, "pretrain_epoch_g": 1, "pretrain_epoch_d": 5, "epoch_gan_d": 5, "epoch_gan_g": 1,
+                     "epoch_surrogate": 50, "filler_num": 36, "lr_g": 0.01, "lr_d": 0.001, "optim_g": "adam", "optim_d": "adam",
+                     "surrogate_model": "WMF", "epoch_s": 50, "unroll_steps_s": 1, "hidden_dim_s": 16, "lr_s": 1e-2,
+                     "weight_decay_s": 1e-5, "batch_size_s": 16, "weight_pos_s": 1.0, "weight_neg_s": 0.0, "selected_ids": [62],
+                     "history_bytes": 1 << 30},
     },
     # recad/default.py:223-228; block / tol / max_iter / seed are this build's solver knobs (block None = 8, or 16 when kVals > 5)
     "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED}},
