@@ -574,7 +574,11 @@ int rk_aush_gen(int32_t n_rows, int32_t filler_num, const int32_t *fcol, const f
  * real / fake = profile * (fillers_mask + selects_mask) with fake[S] = gen + 5 (target_patch at selected_ids, aush.py:121),
  * torch.optim.Adam step adam_t on D (first-layer gradient reduced in (item, row) order: bit-reproducible), then
  * losses[0..4) = d_loss, g_loss_rec, g_loss_shilling, g_loss_gan (with the updated D).  The generator is not changed
- * (aush.py:138 detaches it).  The replay entry: the sample may come from rk_aush_sample with given draws and a given zr. */
+ * (aush.py:138 detaches it).  The replay entry: the sample may come from rk_aush_sample with given draws and a given zr.
+ * Gradient read-out (the per-kernel tests rely on it): with desc->lr = 0, beta1 = beta2 = 0, eps > 0, d_m = d_v = 0 and
+ * adam_t = 1 the Adam element computes m = 0 + 1 * (g - 0) and v = 0 * 0 + 1 * g * g with a step size of 0, so the call leaves
+ * d_m = the gradient of every parameter exactly as the kernels summed it (first-layer rows outside the batch stay 0),
+ * d_v = g * g, d_param unchanged bit for bit, and g_loss_gan evaluated with the unchanged D. */
 int rk_aush_d_step(const rk_aush_desc *desc, int32_t B, const int32_t *fcol, const float *fval, const int32_t *nf, const float *sval,
                    const float *gen, const uint8_t *zr, int32_t adam_t, float *losses, void *stream);
 /* One epoch of Aush.train_step without a host round trip: permutation of eligible[0..n_eligible) (stream_id = epoch), filler

@@ -1,6 +1,7 @@
 """GPU tests of the AUSH attacker (csrc/aush.hip + recad_amd/attack): replay of the reference's own draws on the game
 data (tests/golden/make_golden_aush.py), the device sampler's invariants, determinism, the yelp / c4s shapes against an
 fp64 numpy restatement, and the attack / defence workflows.
+The kernels one entry point at a time, gradients included, are in tests/test_attacker_kernels_gpu.py.
 
 Tolerances.  The device sums in a different order than torch's CPU GEMMs and reductions (sparse first layer, per-thread
 dot products, fp64 loss sums), so values agree to fp32 reordering, not to the bit: losses within 1e-5 relative (each
@@ -15,6 +16,8 @@ import torch
 
 from recad_amd import dataset, model, synth, workflow
 from recad_amd.defense.pca_select_users import flag_count
+
+from ._aush_restate import _restate_batch, adam_step64
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -196,52 +199,7 @@ def test_determinism(gpu_device):
     assert set(np.unique(fake[:, 62]).tolist()) <= {1.0, 2.0, 3.0, 4.0, 5.0}
 
 
-# ---------------------------------------------------------------- fp64 restatement of one train batch (aush.py:128-167)
-def _sig(z):
-    return 1.0 / (1.0 + np.exp(-z))
-
-
-def _restate_batch(D, G, ptr, idx, val, users, draws, zr, S, I, lr, t):
-    """One discriminator step in float64 from the reference's formulas; returns (losses, updated D, Adam state)."""
-    D = {k: v.astype(np.float64) for k, v in D.items()}
-    B = len(users)
-    rows = []
-    for r, u in enumerate(users):
-        c, v = idx[ptr[u]:ptr[u + 1]], val[ptr[u]:ptr[u + 1]]
-        fc = np.unique(draws[r])
-        fv = np.array([v[np.searchsorted(c, x)] for x in fc])
-        sv = np.array([v[np.searchsorted(c, s)] if s in c else 0.0 for s in S])
-        rows.append((fc, fv, sv))
-    W1g, b1g, W2g, b2g = (G[k].astype(np.float64) for k in ("main.0.weight", "main.0.bias", "main.2.weight", "main.2.bias"))
-    gen = np.array([5 * _sig(W2g[S] @ _sig(W1g[:, fc] @ fv + b1g) + b2g[S]) for fc, fv, _ in rows])
-    cols = [np.concatenate([fc, S]) for fc, _, _ in rows]
-    xr = [np.concatenate([fv, sv]) for fc, fv, sv in rows]
-    xf = [np.concatenate([fv, gen[r] + 5]) for r, (fc, fv, sv) in enumerate(rows)]
-
-    def fwd(Dp, cols_, xs):
-        h1 = np.stack([_sig(Dp["main.0.weight"][:, c] @ x + Dp["main.0.bias"]) for c, x in zip(cols_, xs)])
-        h2 = _sig(h1 @ Dp["main.2.weight"].T + Dp["main.2.bias"])
-        h3 = _sig(h2 @ Dp["main.4.weight"].T + Dp["main.4.bias"])
-        return h1, h2, h3, _sig(h3 @ Dp["main.6.weight"].T + Dp["main.6.bias"])[:, 0]
-
-    bce = lambda x, y: -(y * np.maximum(np.log(x), -100) + (1 - y) * np.maximum(np.log1p(-x), -100))
-    allc, allx = cols + cols, xr + xf
-    y = np.concatenate([np.ones(B), np.zeros(B)])
-    h1, h2, h3, x = fwd(D, allc, allx)
-    d_loss = 0.5 * (bce(x[:B], 1).mean() + bce(x[B:], 0).mean())
-    dz4 = (0.5 * (x - y) / np.maximum(x * (1 - x), 1e-12) / B) * (1 - x) * x
-    dz3 = dz4[:, None] * D["main.6.weight"][0][None, :] * (1 - h3) * h3
-    dz2 = (dz3 @ D["main.4.weight"]) * (1 - h2) * h2
-    dz1 = (dz2 @ D["main.2.weight"]) * (1 - h1) * h1
-    grad = {"main.6.weight": (dz4 @ h3)[None, :], "main.6.bias": np.array([dz4.sum()]), "main.4.weight": dz3.T @ h2,
-            "main.4.bias": dz3.sum(0), "main.2.weight": dz2.T @ h1, "main.2.bias": dz2.sum(0), "main.0.bias": dz1.sum(0)}
-    gw1 = {}
-    for r, (c, xs) in enumerate(zip(allc, allx)):
-        for cc, xx in zip(c, xs):
-            gw1[int(cc)] = gw1.get(int(cc), 0.0) + xx * dz1[r]
-    return d_loss, gen, grad, gw1, (lambda Dp: fwd(Dp, cols, xf)[3])
-
-
+# ---------------------------------------------------------------- against the fp64 restatement (tests/_aush_restate.py)
 def test_large_shapes_against_fp64(gpu_device):
     for name in ("yelp", "c4s"):
         d = synth.make_device(name, gpu_device)
@@ -278,23 +236,7 @@ def test_large_shapes_against_fp64(gpu_device):
             assert abs(got[0] - d_loss) <= 1e-5 * abs(d_loss), (name, step, got, d_loss)
             assert abs(got[1] - rec) <= 1e-5 * abs(rec) + 1e-12 and abs(got[2] - shill) <= 1e-5 * abs(shill)
             # Adam (torch.optim.Adam defaults) in fp64 on the restated gradient, then g_loss_gan with the updated D
-            b1, b2, eps, lr = 0.9, 0.999, 1e-8, att.lr_d
-            Dn = {k: v.astype(np.float64).copy() for k, v in D.items()}
-            W1 = Dn["main.0.weight"]
-            for k, gk in list(grad.items()) + [("w1", None)]:
-                if k == "w1":
-                    touched = np.nonzero(np.any(m0["main.0.weight"] != 0, axis=0) | np.isin(np.arange(I), list(gw1)))[0]
-                    gfull = np.zeros((150, len(touched)))
-                    for j, c in enumerate(touched):
-                        if int(c) in gw1:
-                            gfull[:, j] = gw1[int(c)]
-                    m = b1 * m0["main.0.weight"][:, touched] + (1 - b1) * gfull
-                    v = b2 * v0["main.0.weight"][:, touched] + (1 - b2) * gfull ** 2
-                    W1[:, touched] -= lr / (1 - b1 ** t) * m / (np.sqrt(v) / np.sqrt(1 - b2 ** t) + eps)
-                    continue
-                m = b1 * m0[k] + (1 - b1) * gk
-                v = b2 * v0[k] + (1 - b2) * gk ** 2
-                Dn[k] = Dn[k] - lr / (1 - b1 ** t) * m / (np.sqrt(v) / np.sqrt(1 - b2 ** t) + eps)
+            Dn = adam_step64(D, m0, v0, grad, gw1, att.lr_d, t, I)
             xg = fake_fwd(Dn)
             gan = -np.maximum(np.log(xg), -100).mean()
             assert abs(got[3] - gan) <= 1e-5 * abs(gan), (name, step, got[3], gan)

@@ -1,7 +1,8 @@
 """CPU tests of the explicit dataset and the attacker registry (recad_amd/dataset.ExplicitData, recad_amd/attack): the
 reference's construction and counting rules, partial_sample against the reference's own run
 (tests/golden/make_golden_aush.py), the lazy-init contract, the loud failure without a HIP device and the defender's
-rating pass-through."""
+rating pass-through; and the fp64 restatement that the AUSH kernel tests compare against (tests/_aush_restate.py): its
+gradients against torch autograd, its losses against the reference's recorded ones, and the power of its error bounds."""
 import ctypes as C
 import os
 import shutil
@@ -15,6 +16,8 @@ from recad_amd import _lib, dataset, default, model, workflow
 from recad_amd.attack import aush as aush_mod
 from recad_amd.defense.pca_select_users import rating_csr
 from recad_amd.utils import InstantiateFail, NotInstantiatedError
+
+from . import _aush_restate as R
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 KVR = np.array([[0, 1, 4], [0, 3, 5], [2, 1, 2], [2, 1, 3], [1, 0, 1], [2, 6, 5]], dtype=np.int64)   # (2, 1) twice
@@ -200,3 +203,114 @@ def test_golden_fixtures_are_consistent():
         assert int(zr.sum()) == n - int(np.floor(n * (1 - float(g["zr_ratio"]))))
         assert not zr[s_real != 0].any()
         off += B
+
+
+# ---------------------------------------------------------------- the restatement behind tests/test_attacker_kernels_gpu.py
+def _dense(c, values, I):
+    """B x I rows from the sparse entries (columns [B, W] with the sentinel as padding)."""
+    out = np.zeros((c.shape[0], I))
+    for r in range(c.shape[0]):
+        live = c[r] != R.SENTINEL
+        out[r, c[r][live]] = values[r][live]
+    return torch.from_numpy(out)
+
+
+@pytest.mark.parametrize("B,F,S,shared", [(5, 6, 3, False), (4, 5, 3, True), (1, 7, 1, True)])
+def test_restated_gradients_match_autograd(B, F, S, shared):
+    """The reference's discriminator as a float64 torch module on dense B x I rows, loss 0.5 (BCE(D(real), 1) + BCE(D(fake), 0))
+    with the fake rows detached: every restated gradient equals autograd's up to fp64 rounding."""
+    I = 300
+    P = R.craft_params(I, 11, w=1.0, b4=0.5)
+    c = R.craft_rows(B, F, S, I, 12, shared=shared, sel_last=shared)
+    if not shared:
+        assert (c["nf"] == 0).any() and (c["nf"][1] < F)            # a row without fillers, a row with nf < F
+    out = R.d_step_ref(P, I, c["fcol"], c["fval"], c["nf"], c["sval"], c["gen"], c["zr"], c["sel"])
+    v = R.unpack_d(P.astype(np.float64), I)
+    lins = [torch.nn.Linear(I, R.HD), torch.nn.Linear(R.HD, R.HD), torch.nn.Linear(R.HD, R.HD), torch.nn.Linear(R.HD, 1)]
+    net = torch.nn.Sequential(*[m for lin in lins for m in (lin, torch.nn.Sigmoid())]).double()
+    names = ["main.0", "main.2", "main.4", "main.6"]
+    with torch.no_grad():
+        lins[0].weight.copy_(torch.from_numpy(v["W1t"].T.copy()))
+        lins[0].bias.copy_(torch.from_numpy(v["main.0.bias"]))
+        for lin, n in zip(lins[1:], names[1:]):
+            lin.weight.copy_(torch.from_numpy(v[n + ".weight"]))
+            lin.bias.copy_(torch.from_numpy(v[n + ".bias"]))
+    real, fake = _dense(out["ec"], out["ev_r"], I), _dense(out["ec"], out["ev_f"], I).detach()
+    bce = torch.nn.BCELoss()
+    xr, xf = net(real)[:, 0], net(fake)[:, 0]
+    loss = 0.5 * (bce(xr, torch.ones(B, dtype=torch.float64)) + bce(xf, torch.zeros(B, dtype=torch.float64)))
+    loss.backward()
+    assert abs(float(loss.detach()) - out["losses"][0]) <= 1e-12 * out["losses"][0]
+    assert abs(float(bce(xf, torch.ones(B, dtype=torch.float64))) - out["losses"][3]) <= 1e-12 * out["losses"][3]
+    auto = {"main.0.weight": lins[0].weight.grad.numpy().T}
+    mine = {"main.0.weight": R.unpack_d(out["g"], I)["W1t"]}
+    for lin, n in zip(lins, names):
+        auto[n + ".bias"] = lin.bias.grad.numpy()
+        mine[n + ".bias"] = out["grad"][n + ".bias"]
+        if n != "main.0":
+            auto[n + ".weight"] = lin.weight.grad.numpy()
+            mine[n + ".weight"] = out["grad"][n + ".weight"]
+    for k in auto:
+        err = np.abs(auto[k] - mine[k].reshape(auto[k].shape)).max()
+        assert err <= 1e-12 * np.abs(auto[k]).max(), (k, err, np.abs(auto[k]).max())
+    # the per-item table and the packed vector say the same
+    assert np.array_equal(R.unpack_d(out["g"], I)["W1t"][out["items"]], out["gw1"])
+    assert set(out["items"].tolist()) == set(out["ec"][out["ec"] != R.SENTINEL].tolist())
+
+
+def test_restated_losses_match_the_reference_run():
+    """The first batch of the reference's own run on the game data (aush_game_f12): its four losses, g_loss_gan after the
+    discriminator's first Adam step, from the restatement alone."""
+    g = np.load(os.path.join(GOLDEN, "aush_game_f12.npz"))
+    p = np.load(os.path.join(GOLDEN, "aush_game_partial.npz"))
+    ptr, idx, val = _explicit(train_dict=p["train_kvr"], valid_dict=p["valid_kvr"], test_dict=p["test_kvr"]).rating_csr()
+    I, B, S = int(g["n_items"]), int(g["batch_len"][0]), np.sort(g["selected_ids"]).astype(np.int64)
+    torch.manual_seed(int(g["seed"]))
+    G, D = ({k: v.numpy() for k, v in st.items()} for st in aush_mod.init_weights(I))
+    out = R.restate_batch_full(D, G, ptr, idx, val, g["users"][:B], g["draws"][:B], g["zr"][:B], S, I)
+    grad = {k: out["grad"][k].reshape(D[k].shape) for k in R.TAIL}
+    zero = {k: np.zeros(v.shape) for k, v in D.items()}
+    Dn = R.adam_step64(D, zero, zero, grad, {int(c): out["gw1"][j] for j, c in enumerate(out["items"])}, 1e-3, 1, I)
+    gan, _ = R.gan_loss(R.pack_d(Dn), I, *out["rows"], out["gen"], S)
+    got = np.array([out["losses"][0], out["losses"][1], out["losses"][2], gan])
+    assert np.all(np.abs(got - g["losses"][0]) <= 1e-5 * np.abs(g["losses"][0])), (got, g["losses"][0])
+
+
+@pytest.mark.parametrize("B,shared", [(16, True), (7, False), (1, True)])
+def test_error_bounds_see_the_errors_they_are_for(B, shared):
+    """The bounds of the GPU comparison, applied to a deliberately damaged reference: one row's contribution missing from
+    one entry (the entry where that row's contribution has the median size), a factor 2 on a whole tensor, and the fake half
+    missing from one first-layer row must each fall outside; the undamaged values are inside and the bounds pass their cap."""
+    I, F, S = 300, 6, 3
+    P = R.craft_params(I, 21, w=R.CRAFT_W)
+    c = R.craft_rows(B, F, S, I, 22, shared=shared)
+    o = R.d_step_ref(P, I, c["fcol"], c["fval"], c["nf"], c["sval"], c["gen"], c["zr"], c["sel"], R.K_ULP)
+    assert np.abs(o["z4"]).max() < 10
+    r = 2 * B - 1                                              # the last fake row: what a loop that stops one row early drops
+    contrib = {"main.6.weight": o["dz4"][r] * o["h3"][r][None, :], "main.6.bias": o["dz4"][r:r + 1], "main.4.weight": np.outer(o["dz3"][r], o["h2"][r]),
+               "main.4.bias": o["dz3"][r], "main.2.weight": np.outer(o["dz2"][r], o["h1"][r]), "main.2.bias": o["dz2"][r], "main.0.bias": o["dz1"][r]}
+    for k in R.TAIL:
+        ref, bound = o["grad"][k], o["grad_err"][k]
+        assert R.capped(ref, bound) and R.within(ref, ref, bound), k
+        e = np.unravel_index(np.argsort(np.abs(contrib[k]).ravel())[contrib[k].size // 2], ref.shape)
+        bad = ref.copy()
+        bad[e] -= contrib[k][e]
+        assert not R.within(bad, ref, bound), (k, e, contrib[k][e], bound[e])
+        assert not R.within(2 * ref, ref, bound), k
+    ref, bound = o["gw1"], o["gw1_err"]
+    assert R.capped(ref, bound) and not R.within(2 * ref, ref, bound)
+    b = B - 1                                                  # the last row's entries: the end of each of its segments
+    for kk in np.nonzero(o["ec"][b] != R.SENTINEL)[0]:
+        j = int(np.searchsorted(o["items"], o["ec"][b, kk]))
+        whole = o["ev_r"][b, kk] * o["dz1"][b] + o["ev_f"][b, kk] * o["dz1"][B + b]
+        if o["ev_f"][b, kk] == 0:
+            continue                                           # a filler the user has not rated contributes an exact 0
+        e = int(np.argsort(np.abs(whole))[R.HD // 2])
+        for part in (whole, o["ev_f"][b, kk] * o["dz1"][B + b]):   # the row's contribution; its fake half alone
+            bad = ref.copy()
+            bad[j, e] -= part[e]
+            assert not R.within(bad, ref, bound), (int(o["ec"][b, kk]), e)
+    for i in range(4):                                         # losses: a factor 2, and one row's term missing from the mean
+        assert o["loss_err"][i] <= 2.0 ** -10 * abs(o["losses"][i])
+        assert not R.within(2 * o["losses"][i], o["losses"][i], o["loss_err"][i])
+        assert not R.within(o["losses"][i] * (1 - 1 / (4 * B)), o["losses"][i], o["loss_err"][i])
