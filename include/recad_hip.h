@@ -618,19 +618,29 @@ int rk_aia_project(int32_t n, const float *gen, float *x, void *stream);
 /* Steps lo .. hi-1 of one epoch of the surrogate (aia.py:444-461), Adam steps adam_t_lo, adam_t_lo + 1, ...: batch loss
  * sum_r sum_i w (X_ri - p_r . q_i)^2 over the batch's positives, weight decay on every row, one launch per step.  keep_all:
  * step lo + k reads slot k of `slots` and writes slot k + 1 (hi - lo + 1 slots); otherwise two slots, step lo + k reads slot
- * (parity0 + k) & 1 and writes the other. */
+ * (parity0 + k) & 1 and writes the other.  adam_t_lo is the 1-based Adam step number of step lo itself (the first step of a fresh
+ * surrogate has adam_t 1; adam_t_lo < 1 is refused), counted across epochs.  A stored entry with X <= 0 weighs nothing but is
+ * still searched; slot k is only read, and no slot other than the ones named is touched.  RK_EINVAL (nothing launched): dpad not
+ * 16 / 32 / 64, batch outside [1, RK_AIA_MAX_BATCH], n_real > n_rows, lo > hi, hi beyond ceil(n_rows / batch), parity0 not 0 / 1,
+ * a null pointer. */
 int rk_aia_forward(const rk_aia_desc *desc, const int32_t *perm, const int32_t *invperm, int32_t lo, int32_t hi, int32_t adam_t_lo,
                    float *slots, int32_t keep_all, int32_t parity0, void *stream);
 /* The reverse of steps hi-1 down to lo (the unrolled epoch, aia.py:463-482): slots as rk_aia_forward's keep_all (slot k = the
  * input of step lo + k).  adj [3 slots' worth: theta-bar, m-bar, v-bar] is updated in place from the adjoint of step hi's
  * output to that of step lo's input; gbar [(R + n_items) dpad] is scratch; xbar [n_fake_nz] accumulates dF/dX of the fake
- * entries (zero it before the first call).  Where v' == 0 exactly, the 1 / sqrt(v') term of v-bar is taken as 0. */
+ * entries (zero it before the first call).  Where v' == 0 exactly, the 1 / sqrt(v') term of v-bar is taken as 0.  adam_t_lo is
+ * the Adam step number of step lo, as in rk_aia_forward (step lo + k is reversed with adam_t_lo + k).  Of slot k + 1 only m' and v'
+ * are read.  After a one-step call gbar holds the adjoint of that step's gradient (g-bar = (1 - b1) m-hat + 2 (1 - b2) g v-hat).
+ * xbar may be null when n_fake_nz is 0 or there is no fake row.  A range equals its single steps run from hi - 1 down, bit for bit. */
 int rk_aia_reverse(const rk_aia_desc *desc, const int32_t *perm, const int32_t *invperm, int32_t lo, int32_t hi, int32_t adam_t_lo,
                    const float *slots, float *adj, float *gbar, float *xbar, void *stream);
 /* G_loss (aia.py:88-114) of theta = P Q^T into loss[0] and its gradient into adj (zeroed first; P rows of real users and Q rows
  * set, m-bar / v-bar zero).  Pairs (user, target) with train_mat[u, t] == 0, grouped by target: pair_ptr [n_tgt + 1],
  * pair_user / pair_tgt (item id) / pair_slot (target index) [n_pairs]; pidx [n_tgt, n_real] = the pair index or -1; tscale
- * [n_tgt] = 1 / (11 |T_t|) (as float).  work: 3 n_pairs floats. */
+ * [n_tgt] = 1 / (11 |T_t|) (as float).  work: 3 n_pairs floats (scratch).  The rows of adj that belong to fake users (n_real ..
+ * n_rows - 1) stay 0: only real users are pairs.  An item i != t with s_ui == s_ut exactly is inside the mask (>=).  Scores are
+ * shifted by their running maximum before expf, so scores beyond expf's range give a finite loss.  n_tgt <= 0 or n_pairs <= 0 is
+ * refused. */
 int rk_aia_attack_loss(const rk_aia_desc *desc, int32_t n_tgt, const int32_t *tgt, const int32_t *pair_ptr, int32_t n_pairs,
                        const int32_t *pair_user, const int32_t *pair_tgt, const int32_t *pair_slot, const int32_t *pidx,
                        const float *tscale, const float *theta, float *work, float *loss, float *adj, void *stream);
