@@ -595,6 +595,41 @@ int rk_aush_fake_assemble(int32_t n_rows, int32_t n_items, int32_t filler_num, c
                           const int32_t *sel, int32_t n_sel, const float *gen, const int32_t *tgt, int32_t n_tgt, float *pre, float *out,
                           void *stream);
 
+/* The heuristic attackers: average, segment and bandwagon (recad/model/attacker/heuristic.py:85-325, registry
+ * recad/default.py:136-158).  recad_amd/attack/heuristic.py drives these entries.  Pointers are device memory unless a
+ * comment says host. */
+#define RK_HEUR_MAX_FILLER 256    /* filler_num limit (one workgroup draws a row's fillers) */
+#define RK_HEUR_MAX_TARGETS 64    /* target ids per call */
+#define RK_HEUR_MAX_SELECT 64     /* |selected_ids| limit */
+#define RK_HEUR_GLOBAL 0          /* filler values: N(global mean, global std)  (bandwagon, heuristic.py:301-305) */
+#define RK_HEUR_ITEM 1            /* N(item mean, item mean) for a rated item, N(global mean, global std) otherwise (average, :139-145) */
+#define RK_HEUR_ONES 2            /* the value 1 (segment, heuristic.py:217) */
+/* Rating statistics of the nnz stored ratings (col, val) of a rating CSR -- its row structure is not needed --, replacing
+ * heuristic.py:91-98 (one mask over all ratings per distinct item) and the counting half of :245-258: item_count [n_items],
+ * item_mean [n_items] float64 (0 where item_count is 0), global [2] = {mean, population std} of all ratings (np.mean / np.std;
+ * {0, 0} when nnz is 0), n_rated [1] = the number of items with a rating.  All sums are float64.  The per-item sums are float64
+ * atomics, so item_mean may differ between two runs at rounding level; the counts and global are the same on every run.
+ * Asynchronous on the stream. */
+int rk_heur_item_stats(int32_t n_items, int64_t nnz, const int32_t *col, const float *val, int32_t *item_count, double *item_mean,
+                       double *global, int32_t *n_rated, void *stream);
+/* The k most rated items, most rated first, replacing the groupby / sort_values / [::-1] / [:11] of heuristic.py:252-259 (whose
+ * order among equal counts is the unstable sort's; here the larger item id comes first).  Selected on the integer counts.  An
+ * item nobody rated is never returned: ids / counts [k] hold *n_found (host) <= k entries, then -1 / 0.  Synchronous. */
+int rk_heur_popular(int32_t n_items, const int32_t *item_count, int32_t k, int32_t *ids, int32_t *counts, int32_t *n_found, void *stream);
+/* generate_fake (heuristic.py:115-151, 191-220, 274-311): out [attack_num, n_items], every element written.  targets
+ * [n_targets] and selected [n_sel] are HOST arrays.  With rate = attack_num / n_targets (integer), row r < rate * n_targets
+ * rates targets[r / rate] with 5 and the other rows rate no target (none does when rate is 0): the reference's slices.  Every
+ * row rates every selected id 5 and filler_num distinct items outside targets U selected, uniformly drawn, with the mode's
+ * value: a normal one is rounded half to even, then clipped to [1, 5].  item_mean / item_count (rk_heur_item_stats) are read
+ * in the ITEM mode only.  The replay form: draw_cols [attack_num, filler_num] (item ids, distinct and outside targets U
+ * selected in each row: the caller's duty) and draw_vals (the float64 values before rounding; not needed in the ONES mode)
+ * replace every draw.  RK_EINVAL, with nothing launched or written: an id outside [0, n_items), a size outside the limits
+ * above, fewer than filler_num items outside targets U selected, an unknown mode. */
+int rk_heur_generate(int32_t attack_num, int32_t n_items, int32_t filler_num, const int32_t *targets, int32_t n_targets,
+                     const int32_t *selected, int32_t n_sel, int32_t mode, double global_mean, double global_std,
+                     const double *item_mean, const int32_t *item_count, const int32_t *draw_cols, const double *draw_vals,
+                     uint64_t seed, uint64_t stream_id, float *out, void *stream);
+
 /* AIA (recad/model/attacker/aia.py, registry recad/default.py:169-186): the weighted-MF surrogate trained from scratch on every
  * train_step, the reverse pass through its unrolled Adam steps, the attack loss and the generator's Adam step.  The surrogate's
  * data is one CSR of R = n_real + fake rows (the rating CSR, then filler_num slots per fake row holding the projected generator),

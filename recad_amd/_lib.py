@@ -144,6 +144,8 @@ class AiaDesc(C.Structure):
 RK_AIA_MAX_BATCH = 256
 RK_AUSH_HG, RK_AUSH_HD = 128, 150
 RK_AUSH_MAX_FILLER, RK_AUSH_MAX_SELECT, RK_AUSH_MAX_PAIRS = 256, 16, 4096
+RK_HEUR_MAX_FILLER, RK_HEUR_MAX_TARGETS, RK_HEUR_MAX_SELECT = 256, 64, 64
+RK_HEUR_GLOBAL, RK_HEUR_ITEM, RK_HEUR_ONES = 0, 1, 2
 RK_AP_HG, RK_AP_HG_REAL, RK_AP_HD1, RK_AP_HD2 = 128, 125, 512, 128
 RK_AP_D_WORK_PER_ROW = 2 * RK_AP_HD1 + 2 * RK_AP_HD2 + 3
 
@@ -220,6 +222,10 @@ _SIGNATURES = {
     "rk_aush_train_epoch": [C.POINTER(AushDesc), _P, _I32, _P, _P, C.c_uint64, C.c_uint64, C.c_double, _I32, _P, _P, _P, _P, _P, _P,
                             _P, _P, _P],
     "rk_aush_fake_assemble": [_I32, _I32, _I32, _P, _P, _P, _P, _I32, _P, _P, _I32, _P, _P, _P],
+    "rk_heur_item_stats": [_I32, _I64, _P, _P, _P, _P, _P, _P, _P],
+    "rk_heur_popular": [_I32, _P, _I32, _P, _P, C.POINTER(_I32), _P],
+    "rk_heur_generate": [_I32, _I32, _I32, _P, _I32, _P, _I32, _I32, C.c_double, C.c_double, _P, _P, _P, _P, C.c_uint64, C.c_uint64,
+                         _P, _P],
     "rk_aia_project": [_I32, _P, _P, _P],
     "rk_aia_forward": [C.POINTER(AiaDesc), _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P],
     "rk_aia_reverse": [C.POINTER(AiaDesc), _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P],

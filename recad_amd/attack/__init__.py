@@ -1,5 +1,6 @@
 from .aia import AIA
 from .aush import Aush, RandomAttacker
 from .aushplus import AushPlus
+from .heuristic import AverageAttack, BandwagonAttack, SegmentAttack
 
-__all__ = ["AIA", "Aush", "AushPlus", "RandomAttacker"]
+__all__ = ["AIA", "Aush", "AushPlus", "AverageAttack", "BandwagonAttack", "RandomAttacker", "SegmentAttack"]

@@ -1,6 +1,6 @@
 """Default configuration registry for the victim path.
 
-Mirrors the keys and values of the reference's registry for the three victims, the random, AUSH, AIA and AushPlus attackers,
+Mirrors the keys and values of the reference's registry for the three victims, the random, average, segment, bandwagon, AUSH, AIA and AushPlus attackers,
 the PCASelectUsers defender (recad/default.py:103-209,223-228) and the implicit / explicit dataset and workflow knobs the
 hot path reads (recad/default.py:49-99,247-267).  Only what the path needs is present.
 """
@@ -26,6 +26,12 @@ MODEL = {
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},
+        # recad/default.py:136-158; seed as for aush.  The reference's BandwagonAttack reads the segment entry by mistake
+        # (heuristic.py:264-266); here bandwagon reads its own, so an empty selected_ids means the 11 most rated items
+        "average": {"attack_num": 50, "filler_num": 36, "seed": None},
+        "segment": {"attack_num": 50, "filler_num": 36,
+                    "selected_ids": [1153, 2201, 1572, 836, 523, 849, 1171, 344, 857, 1213, 1535], "seed": None},
+        "bandwagon": {"attack_num": 50, "filler_num": 36, "selected_ids": [], "seed": None},
         # recad/default.py:159-168; seed is this build's: the key of the device RNG (None = drawn from np.random at .I())
         "aush": {"attack_num": 50, "filler_num": 36, "lr_g": 0.01, "lr_d": 0.001, "optim_g": "adam", "optim_d": "adam",
                  "selected_ids": [62], "ZR_ratio": 0.2, "seed": None},

@@ -3,7 +3,8 @@ for the victims, attackers and defender this build implements."""
 from . import attack, defense, victim
 
 factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": victim.NCF},
-             "attacker": {"aia": attack.AIA, "aush": attack.Aush, "aushplus": attack.AushPlus, "random": attack.RandomAttacker},
+             "attacker": {"aia": attack.AIA, "aush": attack.Aush, "aushplus": attack.AushPlus, "random": attack.RandomAttacker,
+                          "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack},
              "defender": {"PCASelectUsers": defense.PCASelectUsers}}
 
 
