@@ -27,9 +27,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..utils import VarDim, get_logger
+from ..utils import VarDim
 from ..victim.base import BaseVictim
-from .aush import _train_csr
+from . import _common
 
 _BETAS, _EPS = (0.9, 0.999), 1e-8      # torch.optim.Adam defaults (aia.py:66-68, 263-265)
 
@@ -42,18 +42,8 @@ def draw_templates(ptr, idx, val, attack_num, filler_num):
     """build_network's draws (aia.py:54-63) on a rating CSR: np.random.choice over the users with at least filler_num
     positive ratings, then per template np.random.shuffle of its nonzero columns, the first filler_num kept.
     Returns (users [attack_num], columns [attack_num, filler_num] as drawn, in shuffle order)."""
-    ptr, idx, val = np.asarray(ptr), np.asarray(idx), np.asarray(val)
-    rows = np.repeat(np.arange(len(ptr) - 1), np.diff(ptr))
-    cnt = np.bincount(rows[val > 0], minlength=len(ptr) - 1)      # np.sum(train_array > 0, 1)
-    pool = np.where(cnt >= filler_num)[0]
-    users = np.random.choice(pool, attack_num)
-    cols = np.zeros((attack_num, filler_num), dtype=np.int64)
-    for r, u in enumerate(users):
-        b, e = ptr[u], ptr[u + 1]
-        fillers = idx[b:e][val[b:e] != 0].astype(np.int64)
-        np.random.shuffle(fillers)
-        cols[r] = fillers[:filler_num]
-    return users, cols
+    users, kept = _common.draw_templates(ptr, idx, val, attack_num, filler_num, need_filler_num=True)
+    return users, np.asarray(kept, dtype=np.int64).reshape(attack_num, filler_num)
 
 
 def target_pairs(ptr, idx, val, n_users, targets):
@@ -87,32 +77,14 @@ class AIA(BaseVictim):
 
     def _build(self, attack_num, filler_num, lr_g, optim_g, surrogate_model, epoch_s, unroll_steps_s, hidden_dim_s, lr_s,
                weight_decay_s, batch_size_s, weight_pos_s, weight_neg_s, history_bytes, **config):
-        ds = config.get("dataset")
-        if ds is None:
-            raise ValueError("AIA needs dataset= (an explicit dataset) at .I()")
-        if surrogate_model != "WMF":
-            raise ValueError(f"AIA: surrogate_model {surrogate_model!r} is not supported (only 'WMF', as the reference)")
-        if float(weight_neg_s) != 0.0:
-            raise ValueError(f"AIA: weight_neg_s {weight_neg_s} is not supported (only 0: the loss stays on the positives)")
-        if str(optim_g).lower() != "adam":
-            raise ValueError(f"AIA: optim_g {optim_g!r} is not supported on the device (the reference's default 'adam' is)")
-        if not 1 <= int(hidden_dim_s) <= 64:
-            raise ValueError(f"AIA: hidden_dim_s {hidden_dim_s} must be in [1, 64]")
-        if not 1 <= int(batch_size_s) <= _lib.RK_AIA_MAX_BATCH:
-            raise ValueError(f"AIA: batch_size_s {batch_size_s} must be in [1, {_lib.RK_AIA_MAX_BATCH}]")
-        if not 1 <= int(unroll_steps_s) <= int(epoch_s):
-            raise ValueError(f"AIA: unroll_steps_s {unroll_steps_s} must be in [1, epoch_s = {epoch_s}]")
-        if int(filler_num) < 0 or int(attack_num) <= 0:
-            raise ValueError("AIA: attack_num must be positive and filler_num non-negative")
-        _lib.require_gpu()
-        self.logger = get_logger(__name__, level=config.get("logging_level", 20))
-        self.device = dev = torch.device(config.get("device", "cuda"))
+        self._refuse(config, surrogate_model, weight_neg_s, optim_g, hidden_dim_s, batch_size_s, unroll_steps_s, epoch_s, filler_num,
+                     attack_num)
+        ds, U, I, ptr, idx, val = _common.open_build(self, config)
         self.dataset = ds
         self.attack_num, self.filler_num = int(attack_num), int(filler_num)
         self.lr_g, self.lr_s, self.wd_s, self.w_pos = float(lr_g), float(lr_s), float(weight_decay_s), float(weight_pos_s)
         self.epoch_s, self.unroll, self.dim, self.batch = int(epoch_s), int(unroll_steps_s), int(hidden_dim_s), int(batch_size_s)
         self.history_bytes = int(history_bytes)
-        U, I, ptr, idx, val = _train_csr(ds)
         self.n_users, self.n_items = U, I
         ptr, idx, val = np.asarray(ptr, np.int64), np.asarray(idx, np.int64), np.asarray(val, np.float32)
         self._host_csr = (ptr, idx, val)
@@ -126,32 +98,60 @@ class AIA(BaseVictim):
             tval[r] = val[b:e][np.searchsorted(idx[b:e], scol[r])] if F else tval[r]
         self.template_users = users
         self.template_cols = scol                      # [A, F], ascending per row: the generator's positions
-        self.R = R = U + A
-        self.dpad = _dpad(self.dim)
-        rowptr = np.concatenate([ptr, ptr[-1] + F * np.arange(1, A + 1, dtype=np.int64)])
-        if rowptr[-1] >= 2 ** 31:
-            raise ValueError("AIA: the surrogate's data has too many entries for int32 indices")
-        self.nnz_real = int(ptr[-1])
-        self._rowptr = torch.as_tensor(rowptr.astype(np.int32)).to(dev)
-        self._col = torch.as_tensor(np.concatenate([idx, scol.reshape(-1)]).astype(np.int32)).to(dev)
-        self._x = torch.as_tensor(np.concatenate([val, np.zeros(A * F, np.float32)])).to(dev)
-        self.gen = torch.as_tensor(tval.reshape(-1)).to(dev)     # fake_parameter at the template positions
+        self._surrogate_data(F * np.arange(1, A + 1, dtype=np.int64), scol.reshape(-1), A * F)
+        self.gen = torch.as_tensor(tval.reshape(-1)).to(self.device)     # fake_parameter at the template positions
         self.gen_m = torch.zeros_like(self.gen)
         self.gen_v = torch.zeros_like(self.gen)
         self._g_t = 0
-        self.N = (R + I) * self.dpad
-        d = _lib.AiaDesc()
-        d.n_rows, d.n_real, d.n_items, d.dpad, d.batch, d.n_fake_nz = R, U, I, self.dpad, self.batch, A * F
-        d.nnz_real = self.nnz_real
-        d.rowptr, d.col, d.x = self._rowptr.data_ptr(), self._col.data_ptr(), self._x.data_ptr()
-        d.lr, d.beta1, d.beta2, d.eps, d.wd, d.w_pos = self.lr_s, _BETAS[0], _BETAS[1], _EPS, self.wd_s, self.w_pos
-        self._desc = d
-        self._pairs = {}
         self._project()
         self.last_entry = None
         self.last_xbar = None
         self.last_loss = None
         self.last_history = None
+
+    def _refuse(self, config, surrogate_model, weight_neg_s, optim_g, hidden_dim_s, batch_size_s, unroll_steps_s, epoch_s, filler_num,
+                attack_num):
+        """The settings the surrogate attackers refuse, before a device is asked for; the message names the class being built."""
+        name = type(self).__name__
+        _common.need_dataset(self, config)
+        if surrogate_model != "WMF":
+            raise ValueError(f"{name}: surrogate_model {surrogate_model!r} is not supported (only 'WMF', as the reference)")
+        if float(weight_neg_s) != 0.0:
+            raise ValueError(f"{name}: weight_neg_s {weight_neg_s} is not supported (only 0: the loss stays on the positives)")
+        if str(optim_g).lower() != "adam":
+            raise ValueError(f"{name}: optim_g {optim_g!r} is not supported on the device (the reference's default 'adam' is)")
+        if not 1 <= int(hidden_dim_s) <= 64:
+            raise ValueError(f"{name}: hidden_dim_s {hidden_dim_s} must be in [1, 64]")
+        if not 1 <= int(batch_size_s) <= _lib.RK_AIA_MAX_BATCH:
+            raise ValueError(f"{name}: batch_size_s {batch_size_s} must be in [1, {_lib.RK_AIA_MAX_BATCH}]")
+        if not 1 <= int(unroll_steps_s) <= int(epoch_s):
+            raise ValueError(f"{name}: unroll_steps_s {unroll_steps_s} must be in [1, epoch_s = {epoch_s}]")
+        if int(filler_num) < 0 or int(attack_num) <= 0:
+            raise ValueError(f"{name}: attack_num must be positive and filler_num non-negative")
+
+    def _surrogate_data(self, fake_ptr, fake_col, n_x):
+        """The surrogate's data on the device: the rating CSR (self._host_csr), then the attack_num fake rows ending at
+        nnz_real + fake_ptr with columns fake_col and n_x value slots (0 until the generator fills them).  Sets R, dpad, nnz_real,
+        _rowptr, _col, _x, N, _desc and _pairs."""
+        ptr, idx, val = self._host_csr
+        dev, U, I = self.device, self.n_users, self.n_items
+        self.R = R = U + self.attack_num
+        self.dpad = _dpad(self.dim)
+        rowptr = np.concatenate([ptr, ptr[-1] + fake_ptr])
+        if rowptr[-1] >= 2 ** 31:
+            raise ValueError(f"{type(self).__name__}: the surrogate's data has too many entries for int32 indices")
+        self.nnz_real = int(ptr[-1])
+        self._rowptr = torch.as_tensor(rowptr.astype(np.int32)).to(dev)
+        self._col = torch.as_tensor(np.concatenate([idx, fake_col]).astype(np.int32)).to(dev)
+        self._x = torch.as_tensor(np.concatenate([val, np.zeros(n_x, np.float32)])).to(dev)
+        self.N = (R + I) * self.dpad
+        d = _lib.AiaDesc()
+        d.n_rows, d.n_real, d.n_items, d.dpad, d.batch, d.n_fake_nz = R, U, I, self.dpad, self.batch, len(fake_col)
+        d.nnz_real = self.nnz_real
+        d.rowptr, d.col, d.x = self._rowptr.data_ptr(), self._col.data_ptr(), self._x.data_ptr()
+        d.lr, d.beta1, d.beta2, d.eps, d.wd, d.w_pos = self.lr_s, _BETAS[0], _BETAS[1], _EPS, self.wd_s, self.w_pos
+        self._desc = d
+        self._pairs = {}
 
     # ------------------------------------------------------------------ description (aia.py:72-86)
     def forward(self):

@@ -20,8 +20,9 @@ import torch
 from torch import nn
 
 from .. import _lib
-from ..utils import VarDim, get_logger
+from ..utils import VarDim
 from ..victim.base import BaseVictim
+from ._common import open_build
 
 HG, HD = _lib.RK_AUSH_HG, _lib.RK_AUSH_HD
 _FAKE_STREAM = 1 << 62
@@ -56,20 +57,6 @@ def d_offsets(n_items):
     return o
 
 
-def _train_csr(ds):
-    """(n_users, n_items, ptr, idx, val) of the attack data: an ExplicitData's rating CSR, or the dense train_mat of a
-    foreign dataset with the reference's info_describe()."""
-    if hasattr(ds, "rating_csr"):
-        ptr, idx, val = ds.rating_csr("train")
-        return int(ds.n_users), int(ds.n_items), ptr, idx, val
-    info = ds.info_describe()
-    mat = np.asarray(info["train_mat"], dtype=np.float32)
-    nz = mat != 0
-    ptr = np.zeros(mat.shape[0] + 1, dtype=np.int64)
-    ptr[1:] = np.cumsum(nz.sum(axis=1))
-    return int(mat.shape[0]), int(mat.shape[1]), ptr, np.nonzero(nz)[1].astype(np.int32), mat[nz]
-
-
 class Aush(BaseVictim):
     """``model.from_config("attacker", "aush", **kw)`` keeps the configuration, ``.I(dataset=explicit)`` builds it,
     ``train_step(target_id_list=...)`` runs one epoch and returns (d_loss, g_loss_rec, g_loss_shilling, g_loss_gan) as the
@@ -80,20 +67,14 @@ class Aush(BaseVictim):
     scope = "attacker"
 
     def _build(self, attack_num, filler_num, lr_g, lr_d, optim_g, optim_d, selected_ids, ZR_ratio, seed, **config):
-        ds = config.get("dataset")
-        if ds is None:
-            raise ValueError("Aush needs dataset= (an explicit dataset) at .I()")
-        _lib.require_gpu()
+        ds, U, I, ptr, idx, val = open_build(self, config)
         if str(optim_d).lower() != "adam":
             raise ValueError(f"Aush: optim_d {optim_d!r} is not supported on the device (the reference's default 'adam' is)")
-        self.logger = get_logger(__name__, level=config.get("logging_level", 20))
-        self.device = torch.device(config.get("device", "cuda"))
         self.dataset = ds
         self.attack_num, self.filler_num = int(attack_num), int(filler_num)
         self.selected_ids = list(selected_ids)
         self.ZR_ratio, self.lr_d, self.lr_g = float(ZR_ratio), float(lr_d), float(lr_g)
         self.seed = int(np.random.randint(0, 2 ** 31 - 1) if seed is None else seed)
-        U, I, ptr, idx, val = _train_csr(ds)
         self.n_users, self.n_items = U, I
         self.batch_size = int(getattr(ds, "config", {}).get("batch_size", 256))
         sel = sorted(set(int(s) for s in self.selected_ids))

@@ -34,9 +34,9 @@ import torch
 from torch import nn
 
 from .. import _lib
-from ..utils import VarDim, get_logger
-from .aia import AIA, _BETAS, _EPS, _dpad
-from .aush import _train_csr
+from ..utils import VarDim
+from . import _common
+from .aia import AIA, _BETAS, _EPS
 
 HG, HGR, HD1, HD2 = _lib.RK_AP_HG, _lib.RK_AP_HG_REAL, _lib.RK_AP_HD1, _lib.RK_AP_HD2
 EPSILON = 1e-4           # BaseGenerator.epsilon (aushplus.py:236)
@@ -46,15 +46,7 @@ def draw_templates(ptr, idx, val, attack_num, filler_num):
     """build_network's draws (aushplus.py:24-30) on a rating CSR: np.random.choice over all users, then per template one
     np.random.shuffle of its nonzero columns, the first filler_num kept.  Returns (users [attack_num], list of the kept
     columns per template in shuffle order; a template with fewer ratings keeps them all)."""
-    ptr, idx, val = np.asarray(ptr), np.asarray(idx), np.asarray(val)
-    users = np.random.choice(range(len(ptr) - 1), attack_num)
-    kept = []
-    for u in users:
-        b, e = ptr[u], ptr[u + 1]
-        fillers = idx[b:e][val[b:e] != 0].astype(np.int64)
-        np.random.shuffle(fillers)
-        kept.append(fillers[:filler_num].copy())
-    return users, kept
+    return _common.draw_templates(ptr, idx, val, attack_num, filler_num, need_filler_num=False)
 
 
 def init_weights(n_items):
@@ -168,31 +160,14 @@ class AushPlus(AIA):
     def _build(self, attack_num, filler_num, pretrain_epoch_g, pretrain_epoch_d, epoch_gan_d, epoch_gan_g, epoch_surrogate, lr_g, lr_d,
                optim_g, optim_d, surrogate_model, epoch_s, unroll_steps_s, hidden_dim_s, lr_s, weight_decay_s, batch_size_s,
                weight_pos_s, weight_neg_s, history_bytes, **config):
-        ds = config.get("dataset")
-        if ds is None:
-            raise ValueError("AushPlus needs dataset= (an explicit dataset) at .I()")
-        if surrogate_model != "WMF":
-            raise ValueError(f"AushPlus: surrogate_model {surrogate_model!r} is not supported (only 'WMF', as the reference)")
-        if float(weight_neg_s) != 0.0:
-            raise ValueError(f"AushPlus: weight_neg_s {weight_neg_s} is not supported (only 0: the loss stays on the positives)")
-        if str(optim_g).lower() != "adam":
-            raise ValueError(f"AushPlus: optim_g {optim_g!r} is not supported on the device (the reference's default 'adam' is)")
-        if not 1 <= int(hidden_dim_s) <= 64:
-            raise ValueError(f"AushPlus: hidden_dim_s {hidden_dim_s} must be in [1, 64]")
-        if not 1 <= int(batch_size_s) <= _lib.RK_AIA_MAX_BATCH:
-            raise ValueError(f"AushPlus: batch_size_s {batch_size_s} must be in [1, {_lib.RK_AIA_MAX_BATCH}]")
-        if not 1 <= int(unroll_steps_s) <= int(epoch_s):
-            raise ValueError(f"AushPlus: unroll_steps_s {unroll_steps_s} must be in [1, epoch_s = {epoch_s}]")
-        if int(filler_num) < 0 or int(attack_num) <= 0:
-            raise ValueError("AushPlus: attack_num must be positive and filler_num non-negative")
+        self._refuse(config, surrogate_model, weight_neg_s, optim_g, hidden_dim_s, batch_size_s, unroll_steps_s, epoch_s, filler_num,
+                     attack_num)
         for k, v in (("pretrain_epoch_g", pretrain_epoch_g), ("epoch_gan_d", epoch_gan_d), ("epoch_gan_g", epoch_gan_g),
                      ("epoch_surrogate", epoch_surrogate)):
             if int(v) < 0:
                 raise ValueError(f"AushPlus: {k} {v} must not be negative")
-        _lib.require_gpu()
-        self.logger = get_logger(__name__, level=config.get("logging_level", 20))
-        self.device = dev = torch.device(config.get("device", "cuda"))
-        self.dataset = ds
+        ds, U, I, ptr, idx, val = _common.open_build(self, config)
+        self.dataset, dev = ds, self.device
         self.attack_num, self.filler_num = int(attack_num), int(filler_num)
         self.pretrain_epoch_g, self.epoch_gan_d, self.epoch_gan_g = int(pretrain_epoch_g), int(epoch_gan_d), int(epoch_gan_g)
         self.epoch_surrogate = int(epoch_surrogate)
@@ -201,7 +176,6 @@ class AushPlus(AIA):
         self.epoch_s, self.unroll, self.dim, self.batch = int(epoch_s), int(unroll_steps_s), int(hidden_dim_s), int(batch_size_s)
         self.history_bytes = int(history_bytes)
         self.batch_size = int(getattr(ds, "config", {}).get("batch_size", 256))
-        U, I, ptr, idx, val = _train_csr(ds)
         self.n_users, self.n_items = U, I
         ptr, idx, val = np.asarray(ptr, np.int64), np.asarray(idx, np.int64), np.asarray(val, np.float32)
         self._host_csr = (ptr, idx, val)
@@ -230,24 +204,8 @@ class AushPlus(AIA):
         self._t_scr = {"zbar": f32(nf), "bbar": f32(4 * nf), "eloss": f32(nf), "dpre": f32(A * HG)}
         self._t_din = f32(nf)
         # ---- the surrogate's data: the rating CSR, then the fake rows (AIA's layout with a general rowptr)
-        self.R = R = U + A
-        self.dpad = _dpad(self.dim)
-        rowptr = np.concatenate([ptr, ptr[-1] + trp[1:]])
-        if rowptr[-1] >= 2 ** 31:
-            raise ValueError("AushPlus: the surrogate's data has too many entries for int32 indices")
-        self.nnz_real = int(ptr[-1])
-        self._rowptr = i32(rowptr)
-        self._col = i32(np.concatenate([idx, tcol]))
-        self._x = torch.as_tensor(np.concatenate([val, np.zeros(max(1, nf), np.float32)])).to(dev)
+        self._surrogate_data(trp[1:], tcol, max(1, nf))
         self.gen = self._x[self.nnz_real:self.nnz_real + nf]       # the generator's value at the template entries
-        self.N = (R + I) * self.dpad
-        d = _lib.AiaDesc()
-        d.n_rows, d.n_real, d.n_items, d.dpad, d.batch, d.n_fake_nz = R, U, I, self.dpad, self.batch, nf
-        d.nnz_real = self.nnz_real
-        d.rowptr, d.col, d.x = self._rowptr.data_ptr(), self._col.data_ptr(), self._x.data_ptr()
-        d.lr, d.beta1, d.beta2, d.eps, d.wd, d.w_pos = self.lr_s, _BETAS[0], _BETAS[1], _EPS, self.wd_s, self.w_pos
-        self._desc = d
-        self._pairs = {}
         # ---- the networks (aushplus.py:32-42)
         gs, dstate = init_weights(I)
         self.g_param = pack_generator(gs, I).to(dev)

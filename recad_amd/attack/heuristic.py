@@ -27,9 +27,9 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ..utils import VarDim, get_logger
+from ..utils import VarDim
 from ..victim.base import BaseVictim
-from .aush import _train_csr
+from ._common import open_build
 
 _FAKE_STREAM = 1 << 62
 POPULAR_K = 11      # heuristic.py:259
@@ -46,15 +46,9 @@ class _Heuristic(BaseVictim):
     popular_when_empty = False
 
     def _build(self, attack_num, filler_num, seed, selected_ids=(), **config):
-        ds = config.get("dataset")
-        if ds is None:
-            raise ValueError(f"{type(self).__name__} needs dataset= (an explicit dataset) at .I()")
-        _lib.require_gpu()
-        self.logger = get_logger(__name__, level=config.get("logging_level", 20))
-        self.device = torch.device(config.get("device", "cuda"))
+        _, U, I, ptr, idx, val = open_build(self, config)
         self.attack_num, self.filler_num = int(attack_num), int(filler_num)
         self.seed = int(np.random.randint(0, 2 ** 31 - 1) if seed is None else seed)
-        U, I, ptr, idx, val = _train_csr(ds)
         self.n_users, self.n_items = U, I
         if self.attack_num <= 0:
             raise ValueError("attack_num must be positive")

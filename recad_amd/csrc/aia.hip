@@ -45,17 +45,6 @@ __device__ __forceinline__ float gsum(float v)
     return v;
 }
 
-__device__ __forceinline__ int find_col(const int *__restrict__ col, int b, int e, int c)
-{
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        const int x = col[mid];
-        if (x == c) return mid;
-        if (x < c) b = mid + 1; else e = mid;
-    }
-    return -1;
-}
-
 __device__ __forceinline__ float wt(float x, float w) { return x > 0.f ? w : 0.f; }
 
 // element (row, lane) once its batch part is known
@@ -146,7 +135,7 @@ __global__ __launch_bounds__(256) void wmf_step_kernel(StepArgs a)
         int kpos = -1;
         if (c0 + lane < a.nb) {
             const int rj = a.perm[a.s0 + c0 + lane];
-            kpos = find_col(a.col, a.rowptr[rj], a.rowptr[rj + 1], item);
+            kpos = rk_find_sorted(a.col, a.rowptr[rj], a.rowptr[rj + 1], item);
         }
         const int n = min(DP, a.nb - c0);
         for (int jj = 0; jj < n; ++jj) {
@@ -179,13 +168,6 @@ __device__ __forceinline__ float dotp(const float *p, const float *__restrict__ 
 #pragma unroll
     for (int d = 0; d < DP; ++d) s = __builtin_fmaf(p[d], q[d], s);
     return s;
-}
-
-__device__ __forceinline__ float wsum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // one wave per (target, user) pair: the masked log-sum-exp of z_ui = s_ui [s_ui >= s_ut], and the pair's loss
@@ -267,7 +249,7 @@ __global__ __launch_bounds__(256) void loss_pgrad_kernel(int U, int R, int I, in
     }
 #pragma unroll
     for (int d = 0; d < DP; ++d) {
-        const float v = wsum(acc[d]);
+        const float v = wave_sum(acc[d]);
         if (lane == 0) adj[(long long)u * DP + d] = v;
     }
 }
@@ -297,7 +279,7 @@ __global__ __launch_bounds__(256) void loss_qgrad_kernel(int n_pairs, int R, int
     }
 #pragma unroll
     for (int d = 0; d < DP; ++d) {
-        const float v = wsum(acc[d]);
+        const float v = wave_sum(acc[d]);
         if (lane == 0) adj[(long long)(R + i) * DP + d] = v;
     }
 }
@@ -311,7 +293,7 @@ __global__ void loss_sum_kernel(int n_tgt, const int *__restrict__ pair_ptr, con
         const int b = pair_ptr[tt], e = pair_ptr[tt + 1];
         float s = 0.f;
         for (int k = b + lane; k < e; k += 64) s += ploss[k];
-        s = wsum(s);
+        s = wave_sum(s);
         total += s / (float)(e - b);
     }
     if (lane == 0) out[0] = total / 10.f;

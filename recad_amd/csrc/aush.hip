@@ -24,34 +24,7 @@ constexpr int kSentinel = 0x7fffffff;
 
 __device__ __forceinline__ float sigm(float z) { return 1.0f / (1.0f + expf(-z)); }
 
-__device__ __forceinline__ unsigned long long draw_key(unsigned long long seed, unsigned long long stream, long long row,
-                                                       int draw)
-{
-    return rk_mix64(seed ^ rk_mix64(stream ^ rk_mix64(((unsigned long long)row << 20) ^ (unsigned long long)draw)));
-}
-
-// binary search of item c in the sorted row [b, e) of col; -1 when absent
-__device__ __forceinline__ int find_in_row(const int *__restrict__ col, int b, int e, int c)
-{
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        const int x = col[mid];
-        if (x == c) return mid;
-        if (x < c) b = mid + 1; else e = mid;
-    }
-    return -1;
-}
-
-__device__ __forceinline__ bool in_sorted(const int *__restrict__ a, int n, int c)
-{
-    int b = 0, e = n;
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        if (a[mid] == c) return true;
-        if (a[mid] < c) b = mid + 1; else e = mid;
-    }
-    return false;
-}
+__device__ __forceinline__ bool in_sorted(const int *__restrict__ a, int n, int c) { return rk_find_sorted(a, 0, n, c) >= 0; }
 
 // ---------------------------------------------------------------- eligible users and filler pool
 // pool_cnt[u] = #{rated items of u (value > 0) outside excl} -- the set the reference draws fillers from
@@ -64,8 +37,7 @@ __global__ void pool_count_kernel(int n_users, const int *__restrict__ rowptr, c
     int c = 0;
     for (int k = rowptr[u] + lane; k < rowptr[u + 1]; k += 64)
         c += (val[k] > 0.f && !in_sorted(excl, n_excl, col[k])) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    c = wave_sum(c);
     if (lane == 0) cnt[u] = c;
 }
 
@@ -95,7 +67,7 @@ __global__ void perm_keys_kernel(int n, unsigned long long seed, unsigned long l
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    keys[i] = draw_key(seed, stream, i, 0x7ffff);
+    keys[i] = rk_draw_key(seed, stream, i, 0x7ffff);
     pos[i] = i;
 }
 
@@ -127,7 +99,7 @@ __global__ __launch_bounds__(64) void sample_kernel(int n_rows, const int *__res
             c = draws[(long long)r * F + k];
         } else {
             const int pb = pool_ptr[u], deg = pool_ptr[u + 1] - pb;
-            const unsigned long long x = draw_key(seed, stream, row0 + r, k);
+            const unsigned long long x = rk_draw_key(seed, stream, row0 + r, k);
             c = deg > 0 ? pool_col[pb + (int)(((x >> 32) * (unsigned long long)deg) >> 32)] : kSentinel;
         }
         d[k] = c;
@@ -146,14 +118,14 @@ __global__ __launch_bounds__(64) void sample_kernel(int n_rows, const int *__res
         if (keep[k]) {
             int rank = 0;
             for (int j = 0; j < F; ++j) rank += (keep[j] && d[j] < d[k]) ? 1 : 0;
-            const int p = find_in_row(col, rb, re, d[k]);
+            const int p = rk_find_sorted(col, rb, re, d[k]);
             fcol[o + rank] = d[k];
             fval[o + rank] = p >= 0 ? val[p] : 0.f;
         }
         if (k >= n_keep) { fcol[o + k] = kSentinel; fval[o + k] = 0.f; }
     }
     for (int s = lane; s < n_sel; s += 64) {
-        const int p = find_in_row(col, rb, re, sel[s]);
+        const int p = rk_find_sorted(col, rb, re, sel[s]);
         sval[(long long)r * n_sel + s] = p >= 0 ? val[p] : 0.f;
     }
     if (lane == 0) nf[r] = n_keep;
@@ -172,7 +144,7 @@ __global__ __launch_bounds__(1024) void zr_kernel(int n_rows, int batch, int n_s
     __syncthreads();
     for (int p = threadIdx.x; p < P; p += blockDim.x) {
         const bool z = sval[(long long)r0 * n_sel + p] == 0.f;
-        key[p] = z ? (draw_key(seed, stream ^ 0x5a5a5a5aULL, r0 + p / n_sel, 0x40000 + p % n_sel) | 1ULL) : 0ULL;
+        key[p] = z ? (rk_draw_key(seed, stream ^ 0x5a5a5a5aULL, r0 + p / n_sel, 0x40000 + p % n_sel) | 1ULL) : 0ULL;
         if (z) atomicAdd(&cnt, 1);
     }
     __syncthreads();
@@ -245,16 +217,6 @@ __host__ __device__ inline DOffsets d_offsets(int n_items)
     return o;
 }
 constexpr int kTail = HD + HD * HD + HD + HD * HD + HD + HD + 1;
-
-__device__ __forceinline__ float block_sum_256(float v, float *red)
-{
-    v = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const float t = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return t;
-}
 
 // One block per discriminator row.  mode 0: rows [0, 2B) = real (y = 1) / fake (y = 0), forward + BCE + backward
 // (d_loss = (BCE(D(real), 1) + BCE(D(fake), 0)) / 2, aush.py:147-155); the real blocks also write the batch's entry
@@ -590,15 +552,16 @@ RK_EXPORT int rk_aush_eligible(int32_t n_users, const int32_t *rowptr, const int
     if (n_users <= 0 || !rowptr || !col || !val || (n_excl > 0 && !excl) || n_excl < 0 || !pool_ptr || !pool_col || !eligible || !n_eligible)
         RK_FAIL(RK_EINVAL, "rk_aush_eligible: bad arguments");
     hipStream_t s = (hipStream_t)stream;
+    RkScratch scratch(s);
     int *cnt = nullptr, *flag = nullptr, *n_sel_d = nullptr;
     void *tmp = nullptr;
     size_t scan_b = 0, sel_b = 0;
     RK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_b, (int *)nullptr, (int *)nullptr, n_users + 1, s));
     RK_HIP(hipcub::DeviceSelect::Flagged(nullptr, sel_b, (int *)nullptr, (int *)nullptr, (int *)nullptr, (int *)nullptr, n_users, s));
-    RK_HIP(hipMallocAsync((void **)&cnt, sizeof(int) * ((size_t)n_users + 1), s));
-    RK_HIP(hipMallocAsync((void **)&flag, sizeof(int) * (size_t)n_users, s));
-    RK_HIP(hipMallocAsync((void **)&n_sel_d, sizeof(int) * 2, s));
-    RK_HIP(hipMallocAsync(&tmp, std::max(scan_b, sel_b), s));
+    RK_HIP(scratch.get(&cnt, (size_t)n_users + 1));
+    RK_HIP(scratch.get(&flag, (size_t)n_users));
+    RK_HIP(scratch.get(&n_sel_d, 2));
+    RK_HIP(scratch.bytes(&tmp, std::max(scan_b, sel_b)));
     RK_HIP(hipMemsetAsync(cnt + n_users, 0, sizeof(int), s));
     const dim3 grid((n_users + 3) / 4);
     hipLaunchKernelGGL(pool_count_kernel, grid, dim3(256), 0, s, n_users, rowptr, col, val, excl, n_excl, cnt);
@@ -610,10 +573,6 @@ RK_EXPORT int rk_aush_eligible(int32_t n_users, const int32_t *rowptr, const int
     hipcub::CountingInputIterator<int> ids(0);
     RK_HIP(hipcub::DeviceSelect::Flagged(tmp, sel_b, ids, flag, eligible, n_sel_d, n_users, s));
     RK_HIP(hipMemcpyAsync(n_eligible, n_sel_d, sizeof(int), hipMemcpyDeviceToHost, s));
-    RK_HIP(hipFreeAsync(cnt, s));
-    RK_HIP(hipFreeAsync(flag, s));
-    RK_HIP(hipFreeAsync(n_sel_d, s));
-    RK_HIP(hipFreeAsync(tmp, s));
     RK_HIP(hipStreamSynchronize(s));
     return RK_OK;
 }
@@ -623,27 +582,23 @@ RK_EXPORT int rk_aush_permute(int32_t n, const int32_t *in, uint64_t seed, uint6
     if (n < 0 || (n > 0 && (!in || !out))) RK_FAIL(RK_EINVAL, "rk_aush_permute: bad arguments");
     if (n == 0) return RK_OK;
     hipStream_t s = (hipStream_t)stream;
+    RkScratch scratch(s);
     unsigned long long *keys = nullptr, *ks = nullptr;
     int *pos = nullptr, *ps = nullptr;
     void *tmp = nullptr;
     size_t tb = 0;
     RK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, ks, pos, ps, n, 0, 64, s));
-    RK_HIP(hipMallocAsync((void **)&keys, 8 * (size_t)n, s));
-    RK_HIP(hipMallocAsync((void **)&ks, 8 * (size_t)n, s));
-    RK_HIP(hipMallocAsync((void **)&pos, 4 * (size_t)n, s));
-    RK_HIP(hipMallocAsync((void **)&ps, 4 * (size_t)n, s));
-    RK_HIP(hipMallocAsync(&tmp, tb, s));
+    RK_HIP(scratch.get(&keys, (size_t)n));
+    RK_HIP(scratch.get(&ks, (size_t)n));
+    RK_HIP(scratch.get(&pos, (size_t)n));
+    RK_HIP(scratch.get(&ps, (size_t)n));
+    RK_HIP(scratch.bytes(&tmp, tb));
     hipLaunchKernelGGL(perm_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, (unsigned long long)seed,
                        (unsigned long long)stream_id, keys, pos);
     RK_CHECK_LAUNCH();
     RK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, ks, pos, ps, n, 0, 64, s));
     hipLaunchKernelGGL(gather_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, in, ps, out);
     RK_CHECK_LAUNCH();
-    RK_HIP(hipFreeAsync(keys, s));
-    RK_HIP(hipFreeAsync(ks, s));
-    RK_HIP(hipFreeAsync(pos, s));
-    RK_HIP(hipFreeAsync(ps, s));
-    RK_HIP(hipFreeAsync(tmp, s));
     return RK_OK;
 }
 

@@ -55,12 +55,68 @@ __device__ __forceinline__ float *row2(float *lo, float *hi, int split, int r, i
     return r < split ? lo + (size_t)r * d : hi + (size_t)(r - split) * d;
 }
 
-__device__ __forceinline__ float wave_sum(float v)
+// sum over the 64 lanes of a wave; the xor butterfly leaves the same bits in every lane
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+
+// sum of v over the 256 threads of the block, in a fixed order; every thread gets it.  red: 4 elements of LDS
+template <typename T>
+__device__ __forceinline__ T block_sum_256(T v, T *red)
+{
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const T t = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return t;
+}
+
+// binary search of c in the ascending entries [b, e) of col; the index, or -1 when absent
+__device__ __forceinline__ int rk_find_sorted(const int *__restrict__ col, int b, int e, int c)
+{
+    while (b < e) {
+        const int mid = (b + e) >> 1;
+        const int x = col[mid];
+        if (x == c) return mid;
+        if (x < c) b = mid + 1; else e = mid;
+    }
+    return -1;
+}
+
+// Stream-ordered scratch of one entry point.  get() is hipMallocAsync on the stream; the destructor hands every buffer
+// back with hipFreeAsync on the same stream (errors ignored there), so each early return of RK_HIP / RK_CHECK_LAUNCH
+// frees what was allocated before it.
+struct RkScratch {
+    static constexpr int kMax = 8;
+    hipStream_t stream;
+    void *ptr[kMax];
+    int n = 0;
+    explicit RkScratch(hipStream_t s) : stream(s) {}
+    RkScratch(const RkScratch &) = delete;
+    RkScratch &operator=(const RkScratch &) = delete;
+    ~RkScratch()
+    {
+        for (int i = 0; i < n; ++i) (void)hipFreeAsync(ptr[i], stream);
+    }
+    hipError_t bytes(void **out, size_t n_bytes)
+    {
+        *out = nullptr;
+        if (n == kMax) return hipErrorOutOfMemory;
+        const hipError_t e = hipMallocAsync(out, n_bytes, stream);
+        if (e == hipSuccess && *out) ptr[n++] = *out;
+        return e;
+    }
+    template <typename T>
+    hipError_t get(T **out, size_t count)
+    {
+        return bytes(reinterpret_cast<void **>(out), sizeof(T) * count);
+    }
+};
 
 // Stream-ordered zero fill by a kernel.  Used instead of hipMemsetAsync where the NEXT launch on the stream
 // accumulates into the buffer with atomics: as the trailing node of a replayed hipGraph a memset node was
@@ -132,6 +188,12 @@ __host__ __device__ __forceinline__ unsigned long long rk_mix64(unsigned long lo
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
     return z ^ (z >> 31);
+}
+// random 64 bits of the attackers' samplers, keyed on (seed, stream, row, draw)
+__device__ __forceinline__ unsigned long long rk_draw_key(unsigned long long seed, unsigned long long stream, long long row,
+                                                          int draw)
+{
+    return rk_mix64(seed ^ rk_mix64(stream ^ rk_mix64(((unsigned long long)row << 20) ^ (unsigned long long)draw)));
 }
 // Graph dropout (lightgcn.py:62-71): stored entry `id` of the adjacency survives this step iff its 24-bit
 // uniform is below keep_prob * 2^24.  seed_step = rk_drop_step_seed(base seed, step index).

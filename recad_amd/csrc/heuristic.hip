@@ -23,23 +23,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kMaxPartials = 1024;
 
-__device__ __forceinline__ unsigned long long draw_key(unsigned long long seed, unsigned long long stream, long long row, int draw)
-{
-    return rk_mix64(seed ^ rk_mix64(stream ^ rk_mix64(((unsigned long long)row << 20) ^ (unsigned long long)draw)));
-}
-
-// sum of v over the 256 threads of the block, in a fixed order; every thread gets it
-__device__ __forceinline__ double block_sum_f64(double v, double *red)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double t = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return t;
-}
-
 // ---------------------------------------------------------------- statistics (heuristic.py:91-98)
 // pass 0: cnt[c] += 1, sum[c] += rating for every stored rating, partial[block] = the block's rating sum
 // pass 1: partial[block] = the block's sum of (rating - global mean)^2
@@ -64,7 +47,7 @@ __global__ __launch_bounds__(kBlock) void stats_pass_kernel(int pass, long long 
             acc += v;
         }
     }
-    acc = block_sum_f64(acc, red);
+    acc = block_sum_256(acc, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
@@ -75,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void stats_global_kernel(int pass, int n_pa
     __shared__ double red[kBlock / 64];
     double acc = 0.0;
     for (int b = threadIdx.x; b < n_partial; b += kBlock) acc += partial[b];
-    acc = block_sum_f64(acc, red);
+    acc = block_sum_256(acc, red);
     if (threadIdx.x == 0) {
         const double m = nnz > 0 ? acc / (double)nnz : 0.0;
         global[pass] = pass ? sqrt(m) : m;
@@ -157,7 +140,7 @@ __global__ __launch_bounds__(kBlock) void generate_kernel(int n_items, int F, in
             const int P = n_items - a.n_excl;
             for (int k = 0; k < F; ++k) {
                 const int j = P - F + k;
-                const unsigned long long x = draw_key(seed, stream, r, k);
+                const unsigned long long x = rk_draw_key(seed, stream, r, k);
                 const int cand = (int)(((x >> 32) * (unsigned long long)(j + 1)) >> 32);
                 bool hit = false;
 #pragma unroll
@@ -196,7 +179,7 @@ __global__ __launch_bounds__(kBlock) void generate_kernel(int n_items, int F, in
             } else {
                 double mu = gmean, sd = gstd;
                 if (mode == RK_HEUR_ITEM && (unsigned)c < (unsigned)n_items && item_count[c] > 0) mu = sd = item_mean[c];
-                x = mu + sd * std_normal(draw_key(seed, stream, r, 0x1000 + k), draw_key(seed, stream, r, 0x2000 + k));
+                x = mu + sd * std_normal(rk_draw_key(seed, stream, r, 0x1000 + k), rk_draw_key(seed, stream, r, 0x2000 + k));
             }
             x = fmin(fmax(rint(x), 1.0), 5.0);                   // np.round (half to even), then clip to [1, 5]
         }
@@ -215,8 +198,9 @@ RK_EXPORT int rk_heur_item_stats(int32_t n_items, int64_t nnz, const int32_t *co
         RK_FAIL(RK_EINVAL, "rk_heur_item_stats: bad arguments (n_items %d, nnz %lld)", n_items, (long long)nnz);
     hipStream_t s = (hipStream_t)stream;
     const int grid = (int)std::min<long long>(kMaxPartials, std::max<long long>(1, (nnz + kBlock - 1) / kBlock));
+    RkScratch scratch(s);
     double *partial = nullptr;
-    RK_HIP(hipMallocAsync((void **)&partial, sizeof(double) * (size_t)grid, s));
+    RK_HIP(scratch.get(&partial, (size_t)grid));
     RK_HIP(rk_zero_async(item_count, sizeof(int32_t) * (size_t)n_items, s));
     RK_HIP(rk_zero_async(item_mean, sizeof(double) * (size_t)n_items, s));
     RK_HIP(rk_zero_async(n_rated, sizeof(int32_t), s));
@@ -230,7 +214,6 @@ RK_EXPORT int rk_heur_item_stats(int32_t n_items, int64_t nnz, const int32_t *co
     hipLaunchKernelGGL(stats_item_kernel, dim3((n_items + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n_items, (const int *)item_count,
                        item_mean, n_rated);
     RK_CHECK_LAUNCH();
-    RK_HIP(hipFreeAsync(partial, s));
     return RK_OK;
 }
 
@@ -240,15 +223,16 @@ RK_EXPORT int rk_heur_popular(int32_t n_items, const int32_t *item_count, int32_
     if (n_items <= 0 || k <= 0 || !item_count || !ids || !counts || !n_found)
         RK_FAIL(RK_EINVAL, "rk_heur_popular: bad arguments (n_items %d, k %d)", n_items, k);
     hipStream_t s = (hipStream_t)stream;
+    RkScratch scratch(s);
     unsigned long long *keys = nullptr, *sorted = nullptr;
     int *n_d = nullptr;
     void *tmp = nullptr;
     size_t tb = 0;
     RK_HIP(hipcub::DeviceRadixSort::SortKeysDescending(nullptr, tb, keys, sorted, n_items, 0, 64, s));
-    RK_HIP(hipMallocAsync((void **)&keys, 8 * (size_t)n_items, s));
-    RK_HIP(hipMallocAsync((void **)&sorted, 8 * (size_t)n_items, s));
-    RK_HIP(hipMallocAsync((void **)&n_d, sizeof(int), s));
-    RK_HIP(hipMallocAsync(&tmp, tb, s));
+    RK_HIP(scratch.get(&keys, (size_t)n_items));
+    RK_HIP(scratch.get(&sorted, (size_t)n_items));
+    RK_HIP(scratch.get(&n_d, 1));
+    RK_HIP(scratch.bytes(&tmp, tb));
     RK_HIP(rk_zero_async(n_d, sizeof(int), s));
     hipLaunchKernelGGL(popular_keys_kernel, dim3((n_items + 255) / 256), dim3(256), 0, s, n_items, item_count, keys);
     RK_CHECK_LAUNCH();
@@ -257,10 +241,6 @@ RK_EXPORT int rk_heur_popular(int32_t n_items, const int32_t *item_count, int32_
                        counts, n_d);
     RK_CHECK_LAUNCH();
     RK_HIP(hipMemcpyAsync(n_found, n_d, sizeof(int), hipMemcpyDeviceToHost, s));
-    RK_HIP(hipFreeAsync(keys, s));
-    RK_HIP(hipFreeAsync(sorted, s));
-    RK_HIP(hipFreeAsync(n_d, s));
-    RK_HIP(hipFreeAsync(tmp, s));
     RK_HIP(hipStreamSynchronize(s));
     return RK_OK;
 }

@@ -210,24 +210,22 @@ RK_EXPORT int rk_build_norm_adj(int32_t n_users, int32_t n_items, const int32_t 
     hipLaunchKernelGGL(adj_user_rows_kernel, dim3((n_users + 3) / 4), dim3(256), 0, s, n_users, r_ptr, r_idx, rowptr, col, val);
     RK_CHECK_LAUNCH();
     if (E > 0) {
+        RkScratch scratch(s);
         unsigned long long *keys = nullptr, *sorted = nullptr;
         void *tmp_sort = nullptr;
         size_t tmp_bytes = 0;
         int end_bit = 32;
         while (end_bit < 64 && (1LL << (end_bit - 32)) < (long long)n_items) ++end_bit;
         RK_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, keys, sorted, (int)E, 0, end_bit, s));
-        RK_HIP(hipMallocAsync((void **)&keys, sizeof(unsigned long long) * (size_t)E, s));
-        RK_HIP(hipMallocAsync((void **)&sorted, sizeof(unsigned long long) * (size_t)E, s));
-        RK_HIP(hipMallocAsync(&tmp_sort, tmp_bytes, s));
+        RK_HIP(scratch.get(&keys, (size_t)E));
+        RK_HIP(scratch.get(&sorted, (size_t)E));
+        RK_HIP(scratch.bytes(&tmp_sort, tmp_bytes));
         hipLaunchKernelGGL(adj_edge_keys_kernel, dim3((n_users + 3) / 4), dim3(256), 0, s, n_users, r_ptr, r_idx, keys);
         RK_CHECK_LAUNCH();
         RK_HIP(hipcub::DeviceRadixSort::SortKeys(tmp_sort, tmp_bytes, keys, sorted, (int)E, 0, end_bit, s));
         const int grid = (int)std::min<long long>(((long long)E + 255) / 256, 8192);
         hipLaunchKernelGGL(adj_item_rows_kernel, dim3(grid), dim3(256), 0, s, n_users, (long long)E, sorted, r_ptr, rowptr, col, val);
         RK_CHECK_LAUNCH();
-        RK_HIP(hipFreeAsync(keys, s));
-        RK_HIP(hipFreeAsync(sorted, s));
-        RK_HIP(hipFreeAsync(tmp_sort, s));
     }
     return RK_OK;
 }

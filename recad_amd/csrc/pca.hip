@@ -54,13 +54,14 @@ RK_EXPORT int rk_pca_transpose(int32_t n_rows, int32_t n_cols, const int32_t *ro
     }
     int end_bit = 32;
     while (end_bit < 64 && (1LL << (end_bit - 32)) < (long long)n_cols) ++end_bit;
+    RkScratch scratch(s);
     unsigned long long *keys = nullptr, *sorted = nullptr;
     void *tmp_sort = nullptr;
     size_t tmp_bytes = 0;
     RK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, sorted, val, t_val, (int)nnz, 0, end_bit, s));
-    RK_HIP(hipMallocAsync((void **)&keys, sizeof(unsigned long long) * (size_t)nnz, s));
-    RK_HIP(hipMallocAsync((void **)&sorted, sizeof(unsigned long long) * (size_t)nnz, s));
-    RK_HIP(hipMallocAsync(&tmp_sort, tmp_bytes, s));
+    RK_HIP(scratch.get(&keys, (size_t)nnz));
+    RK_HIP(scratch.get(&sorted, (size_t)nnz));
+    RK_HIP(scratch.bytes(&tmp_sort, tmp_bytes));
     hipLaunchKernelGGL(pca_edge_keys_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, n_rows, rowptr, col, keys);
     RK_CHECK_LAUNCH();
     RK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp_sort, tmp_bytes, keys, sorted, val, t_val, (int)nnz, 0, end_bit, s));
@@ -69,9 +70,6 @@ RK_EXPORT int rk_pca_transpose(int32_t n_rows, int32_t n_cols, const int32_t *ro
     const int grid = (int)std::min<long long>(((long long)nnz + 255) / 256, 8192);
     hipLaunchKernelGGL(pca_t_col_kernel, dim3(grid), dim3(256), 0, s, (long long)nnz, sorted, t_col);
     RK_CHECK_LAUNCH();
-    RK_HIP(hipFreeAsync(keys, s));
-    RK_HIP(hipFreeAsync(sorted, s));
-    RK_HIP(hipFreeAsync(tmp_sort, s));
     return RK_OK;
 }
 
@@ -80,13 +78,6 @@ RK_EXPORT int rk_pca_transpose(int32_t n_rows, int32_t n_cols, const int32_t *ro
 // (sum over the stored entries of (x - mean)^2, plus (n - nnz) * mean^2), rounded to fp32; var < 10 * FLT_EPSILON
 // counts as constant (_handle_zeros_in_scale) and gets scale 1.  One wave per row of A^T; lane-strided sums meet in a
 // fixed butterfly, so the result is deterministic.
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void pca_col_scale_kernel(int n_cols, int n_users, const int *__restrict__ t_rowptr,
                                                             const float *__restrict__ t_val, float *__restrict__ inv_scale,
                                                             float *__restrict__ sigma)
@@ -96,14 +87,14 @@ __global__ __launch_bounds__(256) void pca_col_scale_kernel(int n_cols, int n_us
     const int b = t_rowptr[j], e = t_rowptr[j + 1];
     double s1 = 0.0;
     for (int k = b + lane; k < e; k += 64) s1 += (double)t_val[k];
-    s1 = wave_sum_f64(s1);
+    s1 = wave_sum(s1);
     const double mean = s1 / (double)n_users;
     double s2 = 0.0;
     for (int k = b + lane; k < e; k += 64) {
         const double d = (double)t_val[k] - mean;
         s2 += d * d;
     }
-    s2 = wave_sum_f64(s2);
+    s2 = wave_sum(s2);
     if (lane == 0) {
         const double var = (s2 + (double)(n_users - (e - b)) * mean * mean) / (double)n_users;
         float vf = (float)var;
@@ -224,7 +215,7 @@ __global__ __launch_bounds__(256) void pca_sq_spmv_kernel(int n_rows, const int 
         const double a = (double)val[k];
         s += a * a * (double)w[col[k]];
     }
-    s = wave_sum_f64(s);
+    s = wave_sum(s);
     if (lane == 0) dist[r] = (float)s;
 }
 
@@ -353,15 +344,16 @@ RK_EXPORT int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *or
 {
     if (n <= 0 || m < 0 || m > n || !dist || !order) RK_FAIL(RK_EINVAL, "rk_pca_select: bad arguments");
     hipStream_t s = (hipStream_t)stream;
+    RkScratch scratch(s);
     unsigned long long *keys = nullptr, *sorted = nullptr;
     int *bad = nullptr;
     void *tmp = nullptr;
     size_t tmp_bytes = 0;
     RK_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, tmp_bytes, keys, sorted, n, 0, 64, s));
-    RK_HIP(hipMallocAsync((void **)&keys, sizeof(unsigned long long) * (size_t)n, s));
-    RK_HIP(hipMallocAsync((void **)&sorted, sizeof(unsigned long long) * (size_t)n, s));
-    RK_HIP(hipMallocAsync((void **)&bad, sizeof(int), s));
-    RK_HIP(hipMallocAsync(&tmp, tmp_bytes, s));
+    RK_HIP(scratch.get(&keys, (size_t)n));
+    RK_HIP(scratch.get(&sorted, (size_t)n));
+    RK_HIP(scratch.get(&bad, 1));
+    RK_HIP(scratch.bytes(&tmp, tmp_bytes));
     RK_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
     hipLaunchKernelGGL(pca_select_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, dist, keys, bad);
     RK_CHECK_LAUNCH();
@@ -372,10 +364,6 @@ RK_EXPORT int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *or
     }
     int h_bad = 0;
     RK_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
-    RK_HIP(hipFreeAsync(keys, s));
-    RK_HIP(hipFreeAsync(sorted, s));
-    RK_HIP(hipFreeAsync(bad, s));
-    RK_HIP(hipFreeAsync(tmp, s));
     RK_HIP(hipStreamSynchronize(s));
     if (h_bad) RK_FAIL(RK_EINVAL, "rk_pca_select: %d non-finite distances", h_bad);
     return RK_OK;

@@ -4,10 +4,9 @@
 // stream differs from numpy's (distributional parity is what the tests check).
 #include "common.h"
 
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) { return rk_mix64(z); }
 __device__ __forceinline__ unsigned long long rnd(unsigned long long seed, unsigned long long draw, unsigned k)
 {
-    return mix64(mix64(seed ^ (draw * 0xD1342543DE82EF95ULL)) + k);
+    return rk_mix64(rk_mix64(seed ^ (draw * 0xD1342543DE82EF95ULL)) + k);
 }
 // uniform integer in [0, n) from 64 random bits (multiply-shift, no modulo bias to speak of)
 __device__ __forceinline__ unsigned bounded(unsigned long long r, unsigned n) { return (unsigned)(((r >> 32) * (unsigned long long)n) >> 32); }

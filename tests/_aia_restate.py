@@ -360,7 +360,7 @@ def wmf_facts(case):
     f["zero_rating_ok"] = zr is not None and zr in rows and zr < c.n_real and bool((x[ptr[zr]:ptr[zr + 1]] == 0).any())
     zf = f["zero_fake"]
     f["zero_fake_ok"] = zf in rows and zf >= c.n_real and bool((x[ptr[zf]:ptr[zf + 1]] == 0).any())
-    # find_col lands on the first and on the last entry of a row: a batch row of three or more entries whose two end entries are
+    # rk_find_sorted lands on the first and on the last entry of a row: a batch row of three or more entries whose two end entries are
     # weighed (X > 0) at columns that exist -- the groups of those two items search this row and must find exactly these entries
     f["first_last"] = any(ptr[r + 1] - ptr[r] >= 3 and x[ptr[r]] > 0 and x[ptr[r + 1] - 1] > 0
                           and 0 <= col[ptr[r]] < col[ptr[r + 1] - 1] < c.I for r in rows)

@@ -66,6 +66,24 @@ def test_refusals_name_the_key(kw, key):
         model.from_config("attacker", "aia").I()
 
 
+@pytest.mark.parametrize("kw, key", [
+    ({"surrogate_model": "ItemAE"}, "surrogate_model"),
+    ({"weight_neg_s": 0.5}, "weight_neg_s"),
+    ({"optim_g": "SGD"}, "optim_g"),
+    ({"hidden_dim_s": 65}, "hidden_dim_s"),
+    ({"batch_size_s": 257}, "batch_size_s"),
+    ({"unroll_steps_s": 0}, "unroll_steps_s"),
+    ({"filler_num": -1}, "filler_num"),
+    ({"attack_num": 0}, "attack_num"),
+])
+@pytest.mark.parametrize("name, cls", [("aia", "AIA"), ("aushplus", "AushPlus")])
+def test_shared_refusals_name_the_key_and_the_class(name, cls, kw, key):
+    """The refusals AushPlus takes from AIA: raised before any device is asked for, naming the setting and the class built."""
+    with pytest.raises(InstantiateFail) as err:
+        model.from_config("attacker", name, **kw).I(dataset=_explicit(_ratings()))
+    assert key in str(err.value) and f"{cls}:" in str(err.value)
+
+
 @pytest.mark.parametrize("filler_num", [0, 4, 6])
 def test_template_draw_matches_dense_restatement(filler_num):
     mat = _ratings()
