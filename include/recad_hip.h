@@ -630,6 +630,59 @@ int rk_heur_generate(int32_t attack_num, int32_t n_items, int32_t filler_num, co
                      const double *item_mean, const int32_t *item_count, const int32_t *draw_cols, const double *draw_vals,
                      uint64_t seed, uint64_t stream_id, float *out, void *stream);
 
+/* UBA's target-user budget selection (recad/model/attacker/uba.py:81-140, registry recad/default.py:210-221); its GAN is AUSH's
+ * and uses the rk_aush_* entries.  recad_amd/attack/uba.py drives these entries.  target_users [n_targets] is a HOST array;
+ * every other pointer is device memory unless a comment says host.  A budget step b = 1..budget is the reference's add_num: the
+ * number of copies of each redrawn row it appends (uba.py:92-93, 123).  The redrawn rows of one (b, trial) are a side CSR over
+ * the target users in the caller's order: side_ptr [n_targets + 1], side_col / side_val [side_cap] (item ids ascending; int32
+ * ratings), where side_cap >= the target users' ratings + one entry per target user who has not rated s.
+ * RK_EINVAL with nothing launched or written: no or more than RK_UBA_MAX_TARGETS target users, one listed twice or outside
+ * [0, n_users), s outside [0, n_items), b or budget outside 1..RK_UBA_MAX_BUDGET, side_cap outside [n_targets, n_targets *
+ * n_items], an unknown mode or path, RK_UBA_PATH_LDS with n_users above RK_UBA_LDS_USERS, and in the MATRIX mode a shape whose
+ * scores can exceed 2^53 ((n_users + n_targets * b) * 125 * n_items: sums are int64 and leave as exact doubles). */
+#define RK_UBA_MAX_BUDGET 16      /* budget limit (uba.py:182 reads 6 columns whatever the budget; the build reads `budget`) */
+#define RK_UBA_MAX_TARGETS 64     /* target users per call: one lane of a wave each in the gather */
+#define RK_UBA_TRIALS 10          /* redraws per budget step (uba.py:127) */
+#define RK_UBA_TOPN 10            /* the top-N the selected item must reach (uba.py:102) */
+#define RK_UBA_LDS_USERS 8000     /* n_users up to which a target user's weight vector is kept in LDS (8 bytes each) */
+#define RK_UBA_ELEMENTWISE 0      /* scores = the redrawn row cubed elementwise: uba.py:99 as written */
+#define RK_UBA_MATRIX 1           /* scores = rows target_user_ids of (E @ E @ E)[:M, M:], E the expanded (M+N)^2 matrix (uba.py:95-98) */
+#define RK_UBA_PATH_AUTO 0        /* LDS when n_users <= RK_UBA_LDS_USERS, else WORK */
+#define RK_UBA_PATH_LDS 1         /* weight vectors accumulated and staged in LDS */
+#define RK_UBA_PATH_WORK 2        /* weight vectors accumulated with global atomics in the scratch, read from there */
+/* The stream-ordered scratch one rk_uba_prob call takes (rk_uba_scores takes the same with budget 1): side CSR, counters, the
+ * weight vectors [n_targets, n_users] int64 and the score rows [n_targets, n_items] float64.  Host only, no HIP call. */
+int rk_uba_workspace_bytes(int32_t n_users, int32_t n_items, int32_t n_targets, int32_t side_cap, int32_t budget, int64_t *bytes);
+/* uba.py:86-91 for one (b, trial): every target user's rated items (rowptr / col of the rating CSR with nnz entries, item ids
+ * ascending inside a row) each get an integer uniform in 1..5 -- from rk_mix64 keyed on (seed, b, trial, target index, position
+ * in the side row), or draws[side position] when draws != NULL (replay; laid out like side_val, the entry at s is ignored) --
+ * and s gets 5, inserted in order when the user had not rated it.  The rating CSR is only read.  *status (device, zeroed by
+ * the caller) becomes 1, and nothing else is written, when the rows need more than side_cap entries or a row pointer is out of
+ * order.  Asynchronous. */
+int rk_uba_redraw(int32_t n_users, int32_t n_items, int64_t nnz, const int32_t *rowptr, const int32_t *col, const int32_t *target_users,
+                  int32_t n_targets, int32_t s, int32_t b, int32_t trial, const int32_t *draws, uint64_t seed, int32_t side_cap,
+                  int32_t *side_ptr, int32_t *side_col, int32_t *side_val, int32_t *status, void *stream);
+/* uba.py:95-113 for one redraw as counts: with x_t target user t's score row, counts [3, n_targets] = n_greater = #{j : x_t[j] >
+ * x_t[s]}, n_equal = #{j != s : x_t[j] == x_t[s]}, n_equal_before = the equal ones with j < s; x (optional, [n_targets, n_items]
+ * float64) receives the score rows.  ELEMENTWISE: x_t = the redrawn row cubed.  MATRIX: x_t = sum_v c_v <r'_v, r'_t> r'_v over
+ * all users v of the rating CSC (colptr [n_items + 1], crow / cval [nnz], the transpose of the rating CSR; ratings are
+ * integers), a target user's row taken from the side CSR instead, c_v = 1 + b for a target user and 1 otherwise: the
+ * reference's expanded matrix with its b appended copies per target user, none of it materialised.  Integer arithmetic: exact,
+ * the same on every run.  Asynchronous. */
+int rk_uba_scores(int32_t n_users, int32_t n_items, int64_t nnz, const int32_t *colptr, const int32_t *crow, const float *cval,
+                  const int32_t *target_users, int32_t n_targets, const int32_t *side_ptr, const int32_t *side_col, const int32_t *side_val,
+                  int32_t side_cap, int32_t s, int32_t b, int32_t mode, int32_t path, int32_t *counts, double *x, void *stream);
+/* budget_matrix (uba.py:119-140): for b = 1..budget and RK_UBA_TRIALS trials each, redraw, score and count a hit when
+ * n_greater + n_equal_before < RK_UBA_TOPN; prob_mat [n_targets, budget] (HOST, float64) = hits / RK_UBA_TRIALS and *n_tie
+ * (HOST) = the number of (b, trial, target user) cases with n_greater < RK_UBA_TOPN <= n_greater + n_equal, where the
+ * reference's np.argsort leaves the answer to the order among equal scores.  draws: NULL, or [budget, RK_UBA_TRIALS, side_cap]
+ * replayed draws, each slab laid out like side_val.  Synchronous: one read-back at the end.  RK_EINVAL also when the rows do
+ * not fit side_cap. */
+int rk_uba_prob(int32_t n_users, int32_t n_items, int64_t nnz, const int32_t *rowptr, const int32_t *col, const int32_t *colptr,
+                const int32_t *crow, const float *cval, const int32_t *target_users, int32_t n_targets, int32_t s, int32_t budget,
+                int32_t mode, int32_t path, const int32_t *draws, uint64_t seed, int32_t side_cap, double *prob_mat, int32_t *n_tie,
+                void *stream);
+
 /* AIA (recad/model/attacker/aia.py, registry recad/default.py:169-186): the weighted-MF surrogate trained from scratch on every
  * train_step, the reverse pass through its unrolled Adam steps, the attack loss and the generator's Adam step.  The surrogate's
  * data is one CSR of R = n_real + fake rows (the rating CSR, then filler_num slots per fake row holding the projected generator),

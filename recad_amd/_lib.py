@@ -146,6 +146,9 @@ RK_AUSH_HG, RK_AUSH_HD = 128, 150
 RK_AUSH_MAX_FILLER, RK_AUSH_MAX_SELECT, RK_AUSH_MAX_PAIRS = 256, 16, 4096
 RK_HEUR_MAX_FILLER, RK_HEUR_MAX_TARGETS, RK_HEUR_MAX_SELECT = 256, 64, 64
 RK_HEUR_GLOBAL, RK_HEUR_ITEM, RK_HEUR_ONES = 0, 1, 2
+RK_UBA_MAX_BUDGET, RK_UBA_MAX_TARGETS, RK_UBA_TRIALS, RK_UBA_TOPN, RK_UBA_LDS_USERS = 16, 64, 10, 10, 8000
+RK_UBA_ELEMENTWISE, RK_UBA_MATRIX = 0, 1
+RK_UBA_PATH_AUTO, RK_UBA_PATH_LDS, RK_UBA_PATH_WORK = 0, 1, 2
 RK_AP_HG, RK_AP_HG_REAL, RK_AP_HD1, RK_AP_HD2 = 128, 125, 512, 128
 RK_AP_D_WORK_PER_ROW = 2 * RK_AP_HD1 + 2 * RK_AP_HD2 + 3
 
@@ -226,6 +229,10 @@ _SIGNATURES = {
     "rk_heur_popular": [_I32, _P, _I32, _P, _P, C.POINTER(_I32), _P],
     "rk_heur_generate": [_I32, _I32, _I32, _P, _I32, _P, _I32, _I32, C.c_double, C.c_double, _P, _P, _P, _P, C.c_uint64, C.c_uint64,
                          _P, _P],
+    "rk_uba_workspace_bytes": [_I32, _I32, _I32, _I32, _I32, C.POINTER(_I64)],
+    "rk_uba_redraw": [_I32, _I32, _I64, _P, _P, _P, _I32, _I32, _I32, _I32, _P, C.c_uint64, _I32, _P, _P, _P, _P, _P],
+    "rk_uba_scores": [_I32, _I32, _I64, _P, _P, _P, _P, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, _P, _P],
+    "rk_uba_prob": [_I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, _P, C.c_uint64, _I32, _P, C.POINTER(_I32), _P],
     "rk_aia_project": [_I32, _P, _P, _P],
     "rk_aia_forward": [C.POINTER(AiaDesc), _P, _P, _I32, _I32, _I32, _P, _I32, _I32, _P],
     "rk_aia_reverse": [C.POINTER(AiaDesc), _P, _P, _I32, _I32, _I32, _P, _P, _P, _P, _P],

@@ -2,5 +2,6 @@ from .aia import AIA
 from .aush import Aush, RandomAttacker
 from .aushplus import AushPlus
 from .heuristic import AverageAttack, BandwagonAttack, SegmentAttack
+from .uba import UBA
 
-__all__ = ["AIA", "Aush", "AushPlus", "AverageAttack", "BandwagonAttack", "RandomAttacker", "SegmentAttack"]
+__all__ = ["AIA", "Aush", "AushPlus", "AverageAttack", "BandwagonAttack", "RandomAttacker", "SegmentAttack", "UBA"]

@@ -1,7 +1,7 @@
 """Default configuration registry for the victim path.
 
-Mirrors the keys and values of the reference's registry for the three victims, the random, average, segment, bandwagon, AUSH, AIA and AushPlus attackers,
-the PCASelectUsers defender (recad/default.py:103-209,223-228) and the implicit / explicit dataset and workflow knobs the
+Mirrors the keys and values of the reference's registry for the three victims, the random, average, segment, bandwagon, AUSH, AIA, AushPlus and UBA attackers,
+the PCASelectUsers defender (recad/default.py:103-221,223-228) and the implicit / explicit dataset and workflow knobs the
 hot path reads (recad/default.py:49-99,247-267).  Only what the path needs is present.
 """
 import logging
@@ -47,6 +47,14 @@ MODEL = {
                      "surrogate_model": "WMF", "epoch_s": 50, "unroll_steps_s": 1, "hidden_dim_s": 16, "lr_s": 1e-2,
                      "weight_decay_s": 1e-5, "batch_size_s": 16, "weight_pos_s": 1.0, "weight_neg_s": 0.0, "selected_ids": [62],
                      "history_bytes": 1 << 30},
+        # recad/default.py:210-221; hops and seed are this build's: "elementwise" is uba.py:99 as written, "matrix" the three-hop
+        # product its names promise (attack/uba.py); seed as for aush, also the key of the budget redraws
+        "uba": {"attack_num": 50, "filler_num": 36, "lr_g": 0.01, "lr_d": 0.001, "optim_g": "adam", "optim_d": "adam",
+                "selected_ids": [62], "ZR_ratio": 0.2,
+                "target_user_ids": [741, 225, 289, 338, 308, 244, 605, 86, 46, 570, 208, 972, 21, 284, 578, 616, 103, 981, 18, 383, 432,
+                                    454, 835, 14, 537, 500, 486, 318, 754, 385, 218, 545, 154, 226, 301, 469, 92, 617, 728, 926, 651, 725,
+                                    418, 435, 243, 595, 97, 130, 836, 91],
+                "budget": 6, "hops": "elementwise", "seed": None},
     },
     # recad/default.py:223-228; block / tol / max_iter / seed are this build's solver knobs (block None = 8, or 16 when kVals > 5)
     "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED}},

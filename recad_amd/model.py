@@ -4,7 +4,8 @@ from . import attack, defense, victim
 
 factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": victim.NCF},
              "attacker": {"aia": attack.AIA, "aush": attack.Aush, "aushplus": attack.AushPlus, "random": attack.RandomAttacker,
-                          "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack},
+                          "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack,
+                          "uba": attack.UBA},
              "defender": {"PCASelectUsers": defense.PCASelectUsers}}
 
 
