@@ -415,6 +415,27 @@ int rk_eligible_users(int32_t n_users, const int32_t *seen_ptr, const int32_t *s
  * double, fixed summation order.  out: device double[2]. */
 int rk_pred_shift(const float *score_before, const float *score_after, int64_t n, double *out, void *stream);
 
+/* Held-out ranking quality of the lists rk_score_topk / rk_topk_rows wrote: what BaseTrainer.evaluate_epoch
+ * (recad/model/attacker/aia.py:327-358) walks `metrics` for -- the reference's `metrics` is None, so it has no metric
+ * function -- over the validate / test batches of recad/dataset/implicit.py:462-476, with the conventions of the LightGCN
+ * evaluation code the victim descends from.  top_ids[n, K]: row b is the list of user user_ids[b], -1 pads match nothing;
+ * gt_ptr / gt_idx: CSR of the held-out split indexed by USER ID, item ids ascending and unique within a row (an item that
+ * is also in the user's seen list can never be recommended and still counts in |gt|); ks[nk]: cut-offs in any order,
+ * nk <= 8, clamped to [1, K]; discount[K] = 1 / log2(j + 2) in double (the device evaluates no logarithm).
+ * Per user (every element written): hits[n, nk] = held-out items among the first ks[q] entries, dcg[n, nk] = the sum of
+ * discount[j] over the hit positions j < ks[q], first[n] = position of the first hit among the K entries or -1; a row with
+ * an empty held-out list gets zeros and -1.
+ * out[1 + 5 nk]: out[0] = rows with a non-empty held-out list; then for each q the SUMS over those rows of
+ * recall = hits / |gt|, precision = hits / ks[q], ndcg = dcg / sum_{j < min(ks[q], |gt|)} discount[j], hit = [hits > 0],
+ * mrr = first in [0, ks[q]) ? 1 / (first + 1) : 0 -- the caller divides by out[0].  Double, fixed summation order.
+ * All pointers on the device; two launches on `stream`, no synchronisation, no allocation (capturable).  n == 0: out is
+ * zeroed and nothing else is touched.  RK_EINVAL, nothing launched: n < 0 or n > INT_MAX (rows are indexed in int32),
+ * K outside [1, 256], nk outside [1, 8], a null `out` (also when n == 0: it is the one buffer still written), any other
+ * null pointer when n > 0. */
+int rk_rank_metrics(const int32_t *top_ids, int64_t n, int32_t K, const int32_t *user_ids, const int32_t *gt_ptr,
+                    const int32_t *gt_idx, const int32_t *ks, int32_t nk, const double *discount, int32_t *hits, double *dcg,
+                    int32_t *first, double *out, void *stream);
+
 /* out[b*n_items + i] = <utab[user_ids[b]], itab[i]> (+ ubias[user_ids[b]] + ibias[i] + mean), optionally through
  * nn.Dropout(dropout) on the score -- MF.forward of a module in training mode (mf.py:40-47); feeds rk_topk_rows. */
 int rk_score_matrix(int32_t dim, const float *utab, int32_t nb, const int32_t *user_ids, const float *itab,

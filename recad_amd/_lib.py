@@ -18,6 +18,7 @@ RK_MAX_GRAPH_STEPS = 64
 ABI_VERSION = 9
 RK_LDS_SYNC_WORDS = 2560
 RK_PCA_GRAM_BLOCKS = 256
+RK_RANK_MAX_NK = 8   # cut-offs per rk_rank_metrics call
 
 
 class HipLibraryMissing(RuntimeError):
@@ -203,6 +204,7 @@ _SIGNATURES = {
     "rk_hit_counts": [_P, _I64, _I32, _P, _I32, _P, _P],
     "rk_eligible_users": [_I32, _P, _P, _P, _I32, _P, _P, _P, _P],
     "rk_pred_shift": [_P, _P, _I64, _P, _P],
+    "rk_rank_metrics": [_P, _I64, _I32, _P, _P, _P, _P, _I32, _P, _P, _P, _P, _P, _P],
     "rk_users_rating": [_I32, _P, _I32, _P, _P, _I32, _P, _P],
     "rk_ncf_forward": [C.POINTER(NCFDesc), _P, _P, _P, _I32, _I64, _P, _P],
     "rk_ncf_train_epoch": [C.POINTER(NCFDesc), _P, _P, _P, _I64, _I32, _I32, _P, _I32, _P],

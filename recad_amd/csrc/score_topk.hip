@@ -936,6 +936,174 @@ RK_EXPORT int rk_pred_shift(const float *score_before, const float *score_after,
     return RK_OK;
 }
 
+// ---------------------------------------------------------------- held-out ranking quality: Recall / Precision / NDCG / HitRate / MRR @k
+// What BaseTrainer.evaluate_epoch (aia.py:327-358) would compute from the validate / test batches of implicit.py:462-476 if its
+// `metrics` were not None, over the lists rk_score_topk / rk_topk_rows left in HBM.
+static constexpr int kRankMaxNk = 8;
+
+// One wave per list, four independent waves per workgroup (no workgroup barrier, no LDS, no atomics).  Lane j tests position
+// c * 64 + j of the list by binary search in the user's held-out row; the ballot of a chunk gives the hits below every cut-off
+// by masked popcount (carried from chunk to chunk) and the first hit by its lowest set bit; the discounts of the hit positions
+// are kept per lane under the same masks and summed over the wave once, in double.
+__global__ __launch_bounds__(256) void rank_metrics_rows_kernel(const int *__restrict__ top_ids, long long n, int K, const int *__restrict__ user_ids,
+                                                                const int *__restrict__ gt_ptr, const int *__restrict__ gt_idx,
+                                                                const int *__restrict__ ks, int nk, const double *__restrict__ discount,
+                                                                int *__restrict__ hits, double *__restrict__ dcg, int *__restrict__ first)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long b = (long long)blockIdx.x * 4 + w;
+    if (b >= n) return;
+    const int u = user_ids[b];
+    const int gb = gt_ptr[u], ge = gt_ptr[u + 1];
+    int kk[kRankMaxNk], h[kRankMaxNk];
+    double d[kRankMaxNk];
+#pragma unroll
+    for (int q = 0; q < kRankMaxNk; ++q) {
+        kk[q] = q < nk ? min(max(ks[q], 1), K) : 0;
+        h[q] = 0;
+        d[q] = 0.0;
+    }
+    int fst = -1;
+    if (ge > gb) {
+        const int *row = top_ids + (size_t)b * (size_t)K;
+        for (int c0 = 0; c0 < K; c0 += 64) {
+            const int pos = c0 + lane;
+            const int id = pos < K ? row[pos] : -1;   // (a -1 pad matches nothing)
+            const bool hit = id >= 0 && rk_find_sorted(gt_idx, gb, ge, id) >= 0;
+            const unsigned long long m = __ballot(hit);
+            if (m == 0ULL) continue;
+            if (fst < 0) fst = c0 + __builtin_ctzll(m);
+            const double disc = hit ? discount[pos] : 0.0;
+#pragma unroll
+            for (int q = 0; q < kRankMaxNk; ++q) {
+                const int rem = kk[q] - c0;   // lanes below rem are positions below the cut-off
+                const unsigned long long mask = rem >= 64 ? ~0ULL : rem <= 0 ? 0ULL : (1ULL << rem) - 1ULL;
+                h[q] += __popcll(m & mask);
+                d[q] += lane < rem ? disc : 0.0;
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < kRankMaxNk; ++q) {
+        if (q >= nk) break;
+        const double s = wave_sum(d[q]);
+        if (lane == q) {
+            hits[(size_t)b * nk + q] = h[q];
+            dcg[(size_t)b * nk + q] = s;
+        }
+    }
+    if (lane == 0) first[b] = fst;
+}
+
+// out[0] = rows with a non-empty held-out list; out[1 + 5 q ..] = the sums over those rows of recall, precision, ndcg, hit and mrr at
+// ks[q].  One workgroup, accumulated in double in a fixed order like pred_shift_kernel (strided partial sums, then a tree) =>
+// reproducible.  Every row is read ONCE, all cut-offs in one pass (a row's loads hang off the dependent chain user_ids -> gt_ptr,
+// which a pass per cut-off would pay nk times), with one division per row: 1 / |gt|; 1 / idcg and 1 / (first + 1) are tables in
+// LDS and the precision sum is the exact sum of the hits, divided once.  A row with an empty held-out list holds zeros and -1, so
+// it adds nothing without a branch.  The tree: the 1024 partials of a sum go through LDS, then ONE wave per sum adds sixteen
+// partials per lane in order (lane, lane + 64, ...) and finishes with a single wave butterfly.
+__global__ __launch_bounds__(1024) void rank_metrics_reduce_kernel(long long n, int K, const int *__restrict__ user_ids, const int *__restrict__ gt_ptr,
+                                                                   const int *__restrict__ ks, int nk, const double *__restrict__ discount,
+                                                                   const int *__restrict__ hits, const double *__restrict__ dcg,
+                                                                   const int *__restrict__ first, double *__restrict__ out)
+{
+    constexpr int NQ = kRankMaxNk;
+    __shared__ double disc_s[kMaxK];
+    __shared__ double ridcg[kMaxK + 1];   // 1 / (discount[0] + ... + discount[g - 1]), the sum taken left to right; [0] unused
+    __shared__ double recip[kMaxK];       // 1 / (j + 1)
+    __shared__ double col[6][1024];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    for (int j = tid; j < K; j += 1024) {
+        disc_s[j] = discount[j];
+        recip[j] = 1.0 / (double)(j + 1);
+    }
+    int kk[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) kk[q] = q < nk ? min(max(ks[q], 1), K) : 1;
+    __syncthreads();
+    if (tid == 0) {
+        double s = 0.0;
+        for (int g = 0; g < K; ++g) {
+            s += disc_s[g];
+            ridcg[g + 1] = s;
+        }
+    }
+    __syncthreads();
+    for (int g = 1 + tid; g <= K; g += 1024) ridcg[g] = 1.0 / ridcg[g];
+    __syncthreads();
+    // recall, ndcg, mrr in double; the hits, the rows with a hit and the counted rows as integers, which is exact and half the
+    // registers of doubles (n < 2^31, K <= 256: a thread's share of the hits stays below 2^29)
+    double v[NQ][3];
+    int vi[NQ][2], cnt = 0;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        v[q][0] = v[q][1] = v[q][2] = 0.0;
+        vi[q][0] = vi[q][1] = 0;
+    }
+    for (long long b = tid; b < n; b += 1024) {
+        const int u = user_ids[b];
+        const int g = gt_ptr[u + 1] - gt_ptr[u], f = first[b];
+        cnt += g > 0 ? 1 : 0;
+        const int g1 = max(g, 1);
+        const double rg = 1.0 / (double)g1, rf = f >= 0 ? recip[f] : 0.0;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            if (q >= nk) break;
+            const int hq = hits[b * nk + q];
+            v[q][0] += (double)hq * rg;
+            v[q][1] += dcg[b * nk + q] * ridcg[min(kk[q], g1)];
+            v[q][2] += f < kk[q] ? rf : 0.0;
+            vi[q][0] += hq;
+            vi[q][1] += hq > 0 ? 1 : 0;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        if (q >= nk) break;
+        col[0][tid] = v[q][0];
+        col[1][tid] = (double)vi[q][0];
+        col[2][tid] = v[q][1];
+        col[3][tid] = (double)vi[q][1];
+        col[4][tid] = v[q][2];
+        if (q == 0) col[5][tid] = (double)cnt;
+        __syncthreads();
+        if (w < (q == 0 ? 6 : 5)) {
+            double s = 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) s += col[w][lane + 64 * j];
+            s = wave_sum(s);
+            if (lane == 0) {
+                if (w == 5) out[0] = s;
+                else out[1 + 5 * q + w] = w == 1 ? s / (double)kk[q] : s;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+RK_EXPORT int rk_rank_metrics(const int32_t *top_ids, int64_t n, int32_t K, const int32_t *user_ids, const int32_t *gt_ptr, const int32_t *gt_idx,
+                              const int32_t *ks, int32_t nk, const double *discount, int32_t *hits, double *dcg, int32_t *first, double *out,
+                              void *stream)
+{
+    if (n < 0 || n > INT_MAX) RK_FAIL(RK_EINVAL, "rk_rank_metrics: n = %lld", (long long)n);
+    if (K <= 0 || K > kMaxK) RK_FAIL(RK_EINVAL, "rk_rank_metrics: K must be in [1,%d]", kMaxK);
+    if (nk <= 0 || nk > kRankMaxNk) RK_FAIL(RK_EINVAL, "rk_rank_metrics: nk must be in [1,%d]", kRankMaxNk);
+    if (!out || (n > 0 && (!top_ids || !user_ids || !gt_ptr || !gt_idx || !ks || !discount || !hits || !dcg || !first)))
+        RK_FAIL(RK_EINVAL, "rk_rank_metrics: null pointer");
+    hipStream_t s = (hipStream_t)stream;
+    if (n == 0) {
+        RK_HIP(rk_zero_async(out, sizeof(double) * (size_t)(1 + 5 * nk), s));
+        return RK_OK;
+    }
+    hipLaunchKernelGGL(rank_metrics_rows_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, top_ids, (long long)n, K, user_ids, gt_ptr, gt_idx, ks,
+                       nk, discount, hits, dcg, first);
+    RK_CHECK_LAUNCH();
+    hipLaunchKernelGGL(rank_metrics_reduce_kernel, dim3(1), dim3(1024), 0, s, (long long)n, K, user_ids, gt_ptr, ks, nk, discount, hits, dcg, first,
+                       out);
+    RK_CHECK_LAUNCH();
+    return RK_OK;
+}
+
 // Materialised score block out[b, i] = <utab[user_ids[b]], itab[i]> (+ biases + mean), optionally through nn.Dropout on
 // the score (MF.forward of a module in training mode with dropout > 0, mf.py:47: the workflows score without .eval()).
 RK_EXPORT int rk_score_matrix(int32_t dim, const float *utab, int32_t nb, const int32_t *user_ids, const float *itab,

@@ -111,6 +111,7 @@ class ImplicitData:
         self._net_keys = (np.repeat(np.arange(self.n_users, dtype=np.int64), np.diff(self._net[0])) * self.n_items
                           + self._net[1].astype(np.int64))
         self._train_sorted = None
+        self._heldout_sorted = {}
         self._graph = None
         self._graph_coo = None
         seed = config.get("seed", None)
@@ -177,6 +178,21 @@ class ImplicitData:
         if self._train_sorted is None:
             self._train_sorted = _sorted_unique_rows(*self._csr["train"])
         return self._train_sorted
+
+    def heldout_csr(self, split, device=None):
+        """user -> sorted unique items of the "valid" / "test" split: the ground truth of evaluate.heldout_quality.  Host arrays, or
+        with `device` their int32 copies there; both are made once per split (and device)."""
+        if split not in ("valid", "test"):
+            raise ValueError(f"heldout_csr: split must be 'valid' or 'test', got {split!r}")
+        if split not in self._heldout_sorted:
+            self._heldout_sorted[split] = _sorted_unique_rows(*self._csr[split])
+        if device is None:
+            return self._heldout_sorted[split]
+        key = (split, torch.device(device))
+        if key not in self._heldout_sorted:
+            self._heldout_sorted[key] = tuple(torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int32, device=key[1])
+                                              for a in self._heldout_sorted[split])
+        return self._heldout_sorted[key]
 
     @property
     def allPos(self):

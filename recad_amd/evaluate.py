@@ -5,11 +5,13 @@ Replaces the per-user Python loop + pandas sort of Normal.user_item_model_genera
 users one fp32-MFMA GEMM and one selection kernel.
 """
 import ctypes as C
+from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from . import _lib
+from .utils import get_logger
 
 
 def score_plan(nb, n_items, dim, K, n_targets, request=None):
@@ -122,7 +124,10 @@ class EvalSession:
     (new graph, new dimension), and never used for victims without scoring_tables() (NCF: score_matrix) or with a
     host-synchronising propagation (fuse_layers)."""
 
-    def __init__(self, victim, user_ids, seen_ptr, seen_idx, targets, K=100, topks=(10, 20, 50, 100), chunk=None, request=None, graph=True):
+    def __init__(self, victim, user_ids, seen_ptr, seen_idx, targets, K=100, topks=(10, 20, 50, 100), chunk=None, request=None, graph=True,
+                 quality=None):
+        """quality: None, or the (gt_ptr, gt_idx) CSR of a held-out split (rank_metrics): run() then also launches
+        rk_rank_metrics over top_ids for `topks` -- inside the captured graph -- and returns its sums as quality_out."""
         _lib.require_gpu()
         if not hasattr(victim, "scoring_tables"):
             raise TypeError("EvalSession needs a victim with scoring_tables() (dot-product scoring); use full_catalog_topk")
@@ -163,6 +168,14 @@ class EvalSession:
         self.trank = torch.empty(n, max(T, 1), dtype=torch.int32, device=dev)
         self.ks = torch.as_tensor(list(self.topks), dtype=torch.int32, device=dev)
         self.counts = torch.zeros(max(T, 1), len(self.topks), dtype=torch.int32, device=dev)
+        self.quality = None
+        if quality is not None:
+            disc, qks = _rank_tables(dev, self.K, self.topks)
+            gt_ptr, gt_idx = _heldout_csr_device(quality[0], quality[1], dev)
+            nk = len(self.topks)
+            self.quality = {"gt_ptr": gt_ptr, "gt_idx": gt_idx, "discount": disc, "ks": qks,
+                            "hits": torch.empty(n, nk, dtype=torch.int32, device=dev), "dcg": torch.empty(n, nk, dtype=torch.float64, device=dev),
+                            "first": torch.empty(n, dtype=torch.int32, device=dev), "out": torch.empty(1 + 5 * nk, dtype=torch.float64, device=dev)}
         self.want_graph = bool(graph) and not getattr(victim, "fuse_layers", False)
         self._graph, self._graph_key, self._runs = None, None, 0
 
@@ -205,10 +218,15 @@ class EvalSession:
                 "rk_score_topk")
         if self.T and self.n:
             _lib.check(L.rk_hit_counts(_lib.ptr(self.trank), self.n, self.T, _lib.ptr(self.ks), len(self.topks), _lib.ptr(self.counts), st), "rk_hit_counts")
+        if self.quality is not None:
+            q = self.quality
+            _lib.check(L.rk_rank_metrics(_lib.ptr(self.top_ids), self.n, self.K, _lib.ptr(self.users), _lib.ptr(q["gt_ptr"]), _lib.ptr(q["gt_idx"]),
+                                         _lib.ptr(q["ks"]), len(self.topks), _lib.ptr(q["discount"]), _lib.ptr(q["hits"]), _lib.ptr(q["dcg"]),
+                                         _lib.ptr(q["first"]), _lib.ptr(q["out"]), st), "rk_rank_metrics")
 
     def run(self):
-        """-> dict of device tensors (top_ids [n, K], top_scores, target_score [n, T], target_rank, hit_counts [T, len(topks)]);
-        no synchronisation."""
+        """-> dict of device tensors (top_ids [n, K], top_scores, target_score [n, T], target_rank, hit_counts [T, len(topks)], and
+        with quality= the sums quality_out [1 + 5 len(topks)] of rk_rank_metrics); no synchronisation."""
         self._runs += 1
         self._refresh_static()
         key = (getattr(self.victim, "_handle_key", None), self._static_key)
@@ -231,8 +249,11 @@ class EvalSession:
                     warnings.warn(f"EvalSession: hipGraph capture unavailable ({type(exc).__name__}: {exc}); evaluating with direct launches")
                     self.want_graph, self._graph = False, None
                     torch.cuda.synchronize()
-        return {"top_ids": self.top_ids, "top_scores": self.top_scores, "target_score": self.tscore[:, :self.T],
-                "target_rank": self.trank[:, :self.T], "hit_counts": self.counts[: max(self.T, 0)]}
+        res = {"top_ids": self.top_ids, "top_scores": self.top_scores, "target_score": self.tscore[:, :self.T],
+               "target_rank": self.trank[:, :self.T], "hit_counts": self.counts[: max(self.T, 0)]}
+        if self.quality is not None:
+            res["quality_out"] = self.quality["out"]
+        return res
 
 
 _KS_CACHE = {}
@@ -250,6 +271,107 @@ def hit_counts(target_rank, topks):
     _lib.check(_lib.lib().rk_hit_counts(_lib.ptr(target_rank.contiguous()), n, T, _lib.ptr(ks), len(ks), _lib.ptr(counts),
                                         _lib.stream_ptr()), "rk_hit_counts")
     return counts
+
+
+RANK_METRICS = ("Recall", "Precision", "NDCG", "HitRate", "MRR")   # the order of rk_rank_metrics' sums per cut-off
+_RANK_CACHE = {}
+
+
+def _rank_tables(device, K, topks):
+    """(discount double[K] = 1 / log2(j + 2), ks int32[len(topks)]) on the device, made once per (device, K, topks)."""
+    key = (torch.device(device), int(K), tuple(int(k) for k in topks))
+    tabs = _RANK_CACHE.get(key)
+    if tabs is None:
+        K, ks = key[1], key[2]
+        if not 1 <= len(ks) <= _lib.RK_RANK_MAX_NK:
+            raise ValueError(f"rank_metrics: between 1 and {_lib.RK_RANK_MAX_NK} cut-offs, got {len(ks)}")
+        if any(not 1 <= k <= K for k in ks):   # (the kernel cannot refuse what lives in device memory: it clamps)
+            raise ValueError(f"rank_metrics: every cut-off must be in [1, K = {K}], got {list(ks)}")
+        disc = 1.0 / np.log2(np.arange(K, dtype=np.float64) + 2.0)
+        tabs = _RANK_CACHE[key] = (torch.as_tensor(disc, dtype=torch.float64, device=key[0]), torch.as_tensor(list(ks), dtype=torch.int32, device=key[0]))
+    return tabs
+
+
+def _heldout_csr_device(gt_ptr, gt_idx, device):
+    """The held-out CSR as int32 device tensors: host arrays are made sorted and unique per row, device tensors are taken as such."""
+    if not (torch.is_tensor(gt_ptr) and torch.is_tensor(gt_idx)):
+        from .dataset import _sorted_unique_rows
+        as_np = lambda a: a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        gt_ptr, gt_idx = _sorted_unique_rows(as_np(gt_ptr).astype(np.int64), as_np(gt_idx))
+        gt_ptr, gt_idx = torch.as_tensor(gt_ptr), torch.as_tensor(gt_idx)
+    ptr, idx = (a.to(device=device, dtype=torch.int32).contiguous() for a in (gt_ptr, gt_idx))
+    if idx.numel() == 0:
+        idx = torch.zeros(1, dtype=torch.int32, device=device)
+    return ptr, idx
+
+
+def quality_dict(out, topks):
+    """rk_rank_metrics' host-side `out` as {Recall@k, Precision@k, NDCG@k, HitRate@k, MRR@k for every k, n_quality_users}: the sums
+    divided by the number of counted users (none: NaN, like Normal._evaluate_on_device)."""
+    out = np.asarray(out, dtype=np.float64)
+    cnt = float(out[0])
+    res = OrderedDict()
+    for q, k in enumerate(topks):
+        for j, name in enumerate(RANK_METRICS):
+            res[f"{name}@{int(k)}"] = float(out[1 + 5 * q + j] / cnt) if cnt > 0 else float("nan")
+    res["n_quality_users"] = int(cnt)
+    return res
+
+
+def rank_metrics(top_ids, user_ids, gt_ptr, gt_idx, topks, to_host=True):
+    """Held-out ranking quality of the lists full_catalog_topk left on the device (rk_rank_metrics): row b of top_ids [n, K] is the
+    list of user user_ids[b]; gt_ptr / gt_idx is the CSR of a held-out split indexed by user id (host arrays are sorted and
+    deduplicated here; device tensors are taken as sorted).  to_host=True: an OrderedDict (quality_dict) from ONE read-back of the
+    sums; to_host=False: the device tensors (hits [n, nk], dcg [n, nk], first [n], out [1 + 5 nk]), no synchronisation."""
+    _lib.require_gpu()
+    if not (torch.is_tensor(top_ids) and top_ids.is_cuda and top_ids.dtype == torch.int32 and top_ids.dim() == 2):
+        raise TypeError("rank_metrics: top_ids must be the int32 device tensor [n, K] that full_catalog_topk(to_host=False) returns, got "
+                        + (f"{top_ids.dtype} {tuple(top_ids.shape)} on {top_ids.device}" if torch.is_tensor(top_ids) else type(top_ids).__name__))
+    top_ids = top_ids.contiguous()   # (held by this name until the call below has been enqueued)
+    n, K = top_ids.shape
+    dev = top_ids.device
+    topks = tuple(int(k) for k in topks)
+    disc, ks = _rank_tables(dev, K, topks)
+    ptr, idx = _heldout_csr_device(gt_ptr, gt_idx, dev)
+    users = (user_ids.to(device=dev, dtype=torch.int32) if torch.is_tensor(user_ids)
+             else torch.as_tensor(np.asarray(user_ids), dtype=torch.int32, device=dev)).contiguous()
+    if users.numel() != n:
+        raise ValueError(f"rank_metrics: {n} lists for {users.numel()} users")
+    nk = len(topks)
+    hits = torch.empty(n, nk, dtype=torch.int32, device=dev)
+    dcg = torch.empty(n, nk, dtype=torch.float64, device=dev)
+    first = torch.empty(n, dtype=torch.int32, device=dev)
+    out = torch.empty(1 + 5 * nk, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().rk_rank_metrics(_lib.ptr(top_ids), n, K, _lib.ptr(users), _lib.ptr(ptr), _lib.ptr(idx), _lib.ptr(ks), nk,
+                                          _lib.ptr(disc), _lib.ptr(hits), _lib.ptr(dcg), _lib.ptr(first), _lib.ptr(out), _lib.stream_ptr()),
+               "rk_rank_metrics")
+    if not to_host:
+        return hits, dcg, first, out
+    return quality_dict(out.cpu().numpy(), topks)
+
+
+def heldout_quality(victim, dataset, split="test", topks=(10, 20, 50, 100), users=None, request=None):
+    """How good is this victim: Recall / Precision / NDCG / HitRate / MRR @k of its full-catalogue lists (train items excluded)
+    against the `split` ("valid" | "test") items of every user who has some -- intersected with `users` when given.  Scoring is
+    full_catalog_topk's (all three victims), the metrics rk_rank_metrics'; one read-back."""
+    if split not in ("valid", "test"):
+        raise ValueError(f"heldout_quality: split must be 'valid' or 'test', got {split!r}")
+    if not (hasattr(victim, "scoring_tables") or hasattr(victim, "score_matrix")):
+        raise TypeError(f"heldout_quality needs a victim with scoring_tables() or score_matrix(); {type(victim).__name__} has neither")
+    if dataset.config.get("graph_source") == "reference":
+        get_logger(__name__).warning(f"heldout_quality: graph_source='reference' trains the victim on the test edges; '{split}' quality is not held out")
+    gt_ptr, gt_idx = dataset.heldout_csr(split)
+    ids = np.nonzero(np.diff(gt_ptr) > 0)[0]
+    if users is not None:
+        ids = np.intersect1d(ids, (users.cpu().numpy() if torch.is_tensor(users) else np.asarray(users)).astype(np.int64))
+    ids = ids.astype(np.int32)
+    topks = tuple(int(k) for k in topks)
+    if len(ids) == 0:
+        return quality_dict(np.zeros(1 + 5 * len(topks)), topks)
+    seen_ptr, seen_idx = dataset.train_csr_sorted()
+    res = full_catalog_topk(victim, ids, seen_ptr, seen_idx, np.zeros(0, dtype=np.int32), K=max(topks), to_host=False, request=request)
+    top_ids = res["top_ids"]
+    return rank_metrics(top_ids, ids, *dataset.heldout_csr(split, device=top_ids.device), topks)   # (the device copy is made once per split)
 
 
 def eligible_users_device(seen_ptr, seen_idx, targets, device):

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .default import WORKFLOW
-from .evaluate import eligible_users, eligible_users_device, full_catalog_topk, hit_counts, hr_rows, pred_shift
+from .evaluate import eligible_users, eligible_users_device, full_catalog_topk, heldout_quality, hit_counts, hr_rows, pred_shift
 from .utils import NullProgress, get_logger
 
 
@@ -60,6 +60,8 @@ class Normal:
         self.attacker = config["attacker"].I(dataset=config["attack_data"])
         self.victim = config["victim"].I(dataset=config["victim_data"])
         self.victim_data = config["victim_data"]
+        if config.get("quality_split") not in (None, "valid", "test"):
+            raise ValueError(f"quality_split must be None, 'valid' or 'test', got {config['quality_split']!r}")
         self.logger = get_logger(__name__, level=config["logging_level"])
         self.timings = OrderedDict()
 
@@ -114,13 +116,19 @@ class Normal:
     def _batched(model):
         return hasattr(model, "scoring_tables") or hasattr(model, "score_matrix")
 
-    def normal_evaluate(self, model, model_fake, dataset, target_id_list, topks):
+    def normal_evaluate(self, model, model_fake, dataset, target_id_list, topks, quality_clean=None):
+        """quality_clean: heldout_quality's numbers for `model` on `dataset` at `topks` when the caller already has them
+        (Defense evaluates the clean model twice); None: computed here when quality_split is set."""
         for m in (model, model_fake):
             fwd = m.input_describe()["forward"]
             assert len(fwd) == 2 and "users" in fwd and "items" in fwd, "Expect forward(users, items)"
         ptr, idx = dataset.train_csr_sorted()
         if self._batched(model) and self._batched(model_fake):
-            return self._evaluate_on_device(model, model_fake, ptr, idx, target_id_list, topks)
+            return self._add_quality(self._evaluate_on_device(model, model_fake, ptr, idx, target_id_list, topks), model, model_fake, dataset, topks,
+                                     quality_clean)
+        if self.c.get("quality_split") is not None:   # no batched scoring path: no silent fall-back
+            bad = next(m for m in (model, model_fake) if not self._batched(m))
+            raise TypeError(f"quality_split needs victims with scoring_tables() or score_matrix(); {type(bad).__name__} has neither")
         users = eligible_users(ptr, idx, target_id_list)
         rows, _ = self._rows(model, dataset, users, target_id_list, topks)
         rows_fake, _ = self._rows(model_fake, dataset, users, target_id_list, topks)
@@ -131,6 +139,24 @@ class Normal:
             results[f"HR@{k}"] = float(np.mean(rows[:, 2 + i]))
             results[f"HR@{k} after attack"] = float(np.mean(rows_fake[:, 2 + i]))
         results["n_eval_users"] = int(len(users))
+        return results
+
+    def _add_quality(self, results, model, model_fake, dataset, topks, clean=None):
+        """quality_split set: held-out ranking quality (evaluate.heldout_quality) of the clean model and of the second one
+        (" after attack"), over `dataset`'s real users and train lists -- the injected users have no held-out items and never
+        enter.  `clean`: the clean model's numbers when the caller has them already, so that an execute() computes them once.
+        One read-back per model."""
+        split = self.c.get("quality_split")
+        if split is None:
+            return results
+        if clean is None:
+            clean = heldout_quality(model, dataset, split=split, topks=topks)
+        after = heldout_quality(model_fake, dataset, split=split, topks=topks)
+        for k in topks:
+            for name in ("Recall", "NDCG", "Precision", "HitRate", "MRR"):
+                results[f"{name}@{k}"] = clean[f"{name}@{k}"]
+                results[f"{name}@{k} after attack"] = after[f"{name}@{k}"]
+        results["n_quality_users"] = clean["n_quality_users"]
         return results
 
     def _evaluate_on_device(self, model, model_fake, ptr, idx, target_id_list, topks):
@@ -240,7 +266,11 @@ class Defense(Normal):
         fake_victim = self.victim.reset().I(dataset=fake_dataset).to(dev)
         self.normal_train(fake_victim, self.c["rec_epoch"])
         results = OrderedDict()
-        results["attacked"] = self.normal_evaluate(self.victim, fake_victim, self.victim_data, self.c["target_id_list"], self.c["topks"])
+        # the clean model is evaluated twice: its held-out quality is computed once and handed to both evaluations
+        split = self.c.get("quality_split")
+        clean_q = heldout_quality(self.victim, self.victim_data, split=split, topks=self.c["topks"]) if split is not None else None
+        results["attacked"] = self.normal_evaluate(self.victim, fake_victim, self.victim_data, self.c["target_id_list"], self.c["topks"],
+                                                   quality_clean=clean_q)
         if "train_step" in self.defender.input_describe():
             self.normal_train(self.defender, self.c["defense_epoch"])
         # a defender whose defense_step takes a dataset (PCASelectUsers) is shown the poisoned graph it is meant to clean
@@ -252,7 +282,8 @@ class Defense(Normal):
         self.random_seed_set()
         defended_victim = self.victim.reset().I(dataset=cleaned).to(dev)
         self.normal_train(defended_victim, self.c["rec_epoch"])
-        results["defended"] = self.normal_evaluate(self.victim, defended_victim, self.victim_data, self.c["target_id_list"], self.c["topks"])
+        results["defended"] = self.normal_evaluate(self.victim, defended_victim, self.victim_data, self.c["target_id_list"], self.c["topks"],
+                                                   quality_clean=clean_q)
         results["n_flagged"] = len(flagged)
         self.fake_dataset, self.cleaned_dataset, self.defended_victim = fake_dataset, cleaned, defended_victim
         self.results = results
