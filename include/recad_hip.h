@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define RK_ABI_VERSION 9
+#define RK_ABI_VERSION 10
 #define RK_OK 0
 #define RK_EINVAL (-22)   /* bad argument / unsupported shape */
 #define RK_EHIP (-5)      /* a HIP runtime call failed */
@@ -501,6 +501,70 @@ int rk_ncf_forward(const rk_ncf_desc *desc, const int64_t *users, const int64_t 
 int rk_ncf_train_epoch(const rk_ncf_desc *desc, const int64_t *users, const int64_t *items,
                        const int64_t *labels, int64_t n, int32_t batch, int32_t adam_t0,
                        float *loss_partials, int32_t apply_update, void *stream);
+
+/* ---------------------------------------------------------------- fp32 MFMA GEMM (test and diagnostic entry) */
+/* The kernel instantiations behind the library's one GEMM dispatcher (csrc/gemm.h gemm_f32_launch), as rk_gemm_f32 reports them. */
+#define RK_GEMM_FORM_NONE 0
+#define RK_GEMM_SKINNY 1                 /* gemm_f32_skinny_kernel: 64-tiles, 32-deep chunks, bounds-checked */
+#define RK_GEMM_DEEP_11_64 2             /* gemm_f32_skinny_deep_kernel<MA, MB, BM>: A and B k-contiguous */
+#define RK_GEMM_DEEP_12_64 3             /*   B row-contiguous (dX) */
+#define RK_GEMM_DEEP_22_64 4             /*   A and B row-contiguous (dW) */
+#define RK_GEMM_DEEP_11_32 5
+#define RK_GEMM_DEEP_12_32 6
+#define RK_GEMM_DEEP_22_32 7
+#define RK_GEMM_WIDE_11 8                /* gemm_f32_wide_kernel<1, 1> */
+#define RK_GEMM_WIDE_12 9                /* gemm_f32_wide_kernel<1, 2> */
+#define RK_GEMM_WIDE_11_PLAIN 10         /* gemm_f32_wide_kernel<1, 1, PLAIN> */
+#define RK_GEMM_WIDE_11_PLAIN_GROUPED 11 /* gemm_f32_wide_kernel<1, 1, PLAIN, GROUPED> */
+#define RK_GEMM_TILE128 12               /* gemm_f32_kernel<128, 1, 3> */
+#define RK_GEMM_TILE128_GATHER 13        /* gemm_f32_kernel<128, 1, 3, GATHER> */
+#define RK_GEMM_TILE128_GATHER_PLAIN 14  /* gemm_f32_kernel<128, 1, 3, GATHER, PLAIN> */
+#define RK_GEMM_TUNING_VARIANT 15        /* a form only tuning builds launch */
+
+#define RK_GEMM_POLICY_LAUNCH 0          /* the dispatcher as given */
+#define RK_GEMM_POLICY_AUTO 1            /* NCF's dX policy: whole-K, or parked K-slices added in slice order + epilogue */
+#define RK_GEMM_POLICY_FWD_BLOCKED 2     /* NCF's blocked training forward: 8 k-blocks combined pairwise, + bias, ReLU */
+
+/* One GEMM request, csrc/gemm.h GemmArgs field for field: C[m, n] = epilogue(sum_k A(m, k) * B(n, k)), every sum the chain
+ * s = fmaf(a[k], b[k], s), k = 0..K-1.  All pointers are device pointers; strides are in floats. */
+typedef struct rk_gemm_desc {
+    int32_t M, N, K;
+    int32_t policy;                            /* RK_GEMM_POLICY_* */
+    const float *A; int64_t a_rs, a_cs;        /* A(m, k) = A[row(m) * a_rs + k * a_cs], row(m) = a_ridx ? a_ridx[m] : m */
+    const int32_t *a_ridx;                     /* optional row gather of A (and of row_bias) */
+    int32_t a_rmod, a_roff;                    /* a_rmod > 0 (a_ridx == NULL): row(m) = (m + a_roff) % a_rmod */
+    const float *acc_init; int32_t ld_init, init_base;   /* optional (needs a_rmod > 0): the chain of C(m, n) starts at
+                                                * acc_init[((m + a_roff) / a_rmod - init_base) * ld_init + n] instead of 0 */
+    const float *B; int64_t b_rs, b_cs;        /* B(n, k) = B[n * b_rs + k * b_cs] */
+    float *C; int32_t ldc, reserved0;
+    const float *col_bias;                     /* s + col_bias[n] */
+    const float *row_bias;                     /* (with col_bias) ((s + row_bias[row(m)]) + col_bias[n]) + const_add */
+    float const_add;
+    int32_t relu;                              /* max(s, 0) */
+    int32_t sigmoid;                           /* 1 / (1 + expf(-s)) */
+    uint32_t drop_thresh24;                    /* > 0: keep element (m, n) iff the counter hash of m * N + n under drop_seed is */
+    float drop_scale; int32_t reserved1;       /*      below drop_thresh24 (= keep_prob * 2^24); kept values times drop_scale */
+    uint64_t drop_seed;
+    const float *mask; int32_t ldmask, reserved2;   /* keep s only where mask[m * ldmask + n] > 0 */
+    float *sk_part; int64_t sk_stride;         /* split_k > 1: slice q STORES its partial at sk_part[q * sk_stride + m * ldc + n];
+                                                * NULL: every slice ADDS its partial into C (float atomics, order not fixed) */
+    int32_t split_k, reserved3;                /* > 1: requested K-slices (no epilogue; 64-tile forms only).  K <= 32 is one
+                                                * chunk, hence one slice: it STORES its whole-K result like split_k <= 1 */
+    float *scratch; int64_t scratch_floats;    /* policies 1 and 2: the K-slice workspace (rk_ncf_desc.gemm_scratch) */
+} rk_gemm_desc;
+
+/* TEST AND DIAGNOSTIC ENTRY: runs one GEMM through the very dispatcher and host policies the NCF tower and the scoring paths
+ * use, and reports which kernel took it -- so a test can pin every form against the k-ordered chain at the element.  No
+ * product path calls it.  policy 0 hands the request to the dispatcher as given; policy 1 is the tower's dX policy
+ * (contiguous C and mask: ldc == ldmask == N; col_bias / relu / mask only; scratch == NULL or N % 4 != 0: whole-K); policy 2
+ * is the blocked training forward (A and B k-contiguous and dense, K % 256 == 0, N % 4 == 0, col_bias optional, relu
+ * REQUIRED, scratch of >= 8 * 64 * N floats: less makes it fail with RK_EINVAL).
+ * form_out (nullable, int32[2]): RK_GEMM_* of the launch and of the right strip's launch (0 where there is none: only
+ * RK_GEMM_WIDE_12 hands a strip on).  splits_out (nullable): the K-slices actually used (1 = whole-K).
+ * RK_EINVAL, nothing launched: a request the kernels would read or write out of bounds for (missing operand, ldc / ldmask /
+ * ld_init < N, row_bias without col_bias, acc_init without a_rmod, an epilogue or a gather together with split_k, parked
+ * slices that overlap) or that the policy does not take. */
+int rk_gemm_f32(const rk_gemm_desc *desc, int32_t *form_out, int32_t *splits_out, void *stream);
 
 /* ---------------------------------------------------------------- defender --------- */
 /* PCASelectUsers (recad/model/defense/PCASelectUsers.py:47-93, registry recad/default.py:223-228) without the dense

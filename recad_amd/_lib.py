@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librecad_hip.so")
 RK_LOSS_PARTIALS = 256
 RK_MAX_GRAPH_STEPS = 64
-ABI_VERSION = 9
+ABI_VERSION = 10
 RK_LDS_SYNC_WORDS = 2560
 RK_PCA_GRAM_BLOCKS = 256
 RK_RANK_MAX_NK = 8   # cut-offs per rk_rank_metrics call
@@ -116,6 +116,32 @@ class NCFDesc(C.Structure):
     ]
 
 
+class GemmDesc(C.Structure):
+    """rk_gemm_desc (include/recad_hip.h): one request of rk_gemm_f32, the test and diagnostic entry of the fp32 MFMA GEMM."""
+
+    _fields_ = [
+        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("policy", C.c_int32),
+        ("A", C.c_void_p), ("a_rs", C.c_int64), ("a_cs", C.c_int64),
+        ("a_ridx", C.c_void_p), ("a_rmod", C.c_int32), ("a_roff", C.c_int32),
+        ("acc_init", C.c_void_p), ("ld_init", C.c_int32), ("init_base", C.c_int32),
+        ("B", C.c_void_p), ("b_rs", C.c_int64), ("b_cs", C.c_int64),
+        ("C", C.c_void_p), ("ldc", C.c_int32), ("reserved0", C.c_int32),
+        ("col_bias", C.c_void_p), ("row_bias", C.c_void_p),
+        ("const_add", C.c_float), ("relu", C.c_int32), ("sigmoid", C.c_int32),
+        ("drop_thresh24", C.c_uint32), ("drop_scale", C.c_float), ("reserved1", C.c_int32), ("drop_seed", C.c_uint64),
+        ("mask", C.c_void_p), ("ldmask", C.c_int32), ("reserved2", C.c_int32),
+        ("sk_part", C.c_void_p), ("sk_stride", C.c_int64), ("split_k", C.c_int32), ("reserved3", C.c_int32),
+        ("scratch", C.c_void_p), ("scratch_floats", C.c_int64),
+    ]
+
+
+# RK_GEMM_* (include/recad_hip.h): the kernel instantiation rk_gemm_f32 reports, by value
+RK_GEMM_FORMS = ("none", "skinny", "deep<1,1,64>", "deep<1,2,64>", "deep<2,2,64>", "deep<1,1,32>", "deep<1,2,32>", "deep<2,2,32>",
+                 "wide<1,1>", "wide<1,2>", "wide<1,1,PLAIN>", "wide<1,1,PLAIN,GROUPED>", "tile128", "tile128<GATHER>",
+                 "tile128<GATHER,PLAIN>", "tuning-variant")
+RK_GEMM_POLICY_LAUNCH, RK_GEMM_POLICY_AUTO, RK_GEMM_POLICY_FWD_BLOCKED = 0, 1, 2
+
+
 class AushDesc(C.Structure):
     """rk_aush_desc (include/recad_hip.h)."""
 
@@ -208,6 +234,7 @@ _SIGNATURES = {
     "rk_users_rating": [_I32, _P, _I32, _P, _P, _I32, _P, _P],
     "rk_ncf_forward": [C.POINTER(NCFDesc), _P, _P, _P, _I32, _I64, _P, _P],
     "rk_ncf_train_epoch": [C.POINTER(NCFDesc), _P, _P, _P, _I64, _I32, _I32, _P, _I32, _P],
+    "rk_gemm_f32": [C.POINTER(GemmDesc), C.POINTER(_I32), C.POINTER(_I32), _P],
     "rk_mf_train_epoch": [_I32, _I32, _I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I64, _I32, _I32, _F, _F, _F,
                           _F, _P, _I32, _F, C.c_uint64, _P],
     "rk_pca_transpose": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P],

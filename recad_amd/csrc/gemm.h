@@ -43,6 +43,8 @@ struct GemmArgs {
                                            // no bias/relu/mask; float atomics => summation order not fixed)
 };
 
+static_assert(RK_GEMM_DEEP_22_32 == RK_GEMM_DEEP_11_64 + 5 && RK_GEMM_WIDE_11_PLAIN_GROUPED == RK_GEMM_WIDE_11 + 3, "gemm_f32_launch reports forms by table index");
+
 static constexpr int kGK = 32, kGLd = kGK + 1;
 template <int BT> constexpr int gemm_lds_bytes(int nbuf) { return nbuf * 2 * BT * kGLd * (int)sizeof(float); }
 
@@ -888,9 +890,13 @@ static __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2
     }
 }
 
-// asynchronous launch; returns the hipError_t of the launch
-inline hipError_t gemm_f32_launch(const GemmArgs &g, hipStream_t s)
+// asynchronous launch; returns the hipError_t of the launch.  form_out (optional, int[2]): the RK_GEMM_* value
+// (include/recad_hip.h) of the instantiation chosen, and of the right strip's launch where there is one (else 0) --
+// read by rk_gemm_f32 (ncf.hip), the test and diagnostic entry; no product caller passes it.
+inline hipError_t gemm_f32_launch(const GemmArgs &g, hipStream_t s, int *form_out = nullptr)
 {
+    if (form_out) form_out[0] = form_out[1] = RK_GEMM_FORM_NONE;
+    auto report = [&](int form) { if (form_out) form_out[0] = form; };
     static RkPerDeviceOnce attr_once;
     static const int variant = RK_TUNE_INT("RK_GEMM_VARIANT", 0);
     int attr_dev;
@@ -916,7 +922,7 @@ inline hipError_t gemm_f32_launch(const GemmArgs &g, hipStream_t s)
         // (A row-contiguous with B k-contiguous has no caller: forward / dX / dW are <1,1>, <1,2>, <2,2>)
         const bool deep = !no_deep && variant != 4 && fa && fb && !(fa == 2 && fb == 1) && g.M % 64 == 0 && g.N % 64 == 0 && g.K % kDK == 0 && per % 4 == 0 &&
                           per * kGK >= deep_min_k;
-        if (variant == 4) hipLaunchKernelGGL((gemm_f32_kernel<64, 1, 4>), dim3(nwg, splits), dim3(256), gemm_lds_bytes<64>(1), s, g2, 1);
+        if (variant == 4) { report(RK_GEMM_TUNING_VARIANT); hipLaunchKernelGGL((gemm_f32_kernel<64, 1, 4>), dim3(nwg, splits), dim3(256), gemm_lds_bytes<64>(1), s, g2, 1); }
         else if (deep) {
             static const int no_half = RK_TUNE_INT("RK_GEMM_NO_HALF", 0);   // A/B only
             const bool half = nwg * splits < 256 && !no_half;   // fewer workgroups than CUs: 32-row tiles
@@ -939,8 +945,9 @@ inline hipError_t gemm_f32_launch(const GemmArgs &g, hipStream_t s)
             const dim3 grid(half ? 2 * nwg : nwg, splits);
             const int which = (half ? 3 : 0) + (fa == 2 ? 2 : fb == 2 ? 1 : 0);
             void *params[1] = {const_cast<GemmArgs *>(&g2)};
+            report(RK_GEMM_DEEP_11_64 + which);   // (RK_GEMM_DEEP_* are numbered in fn's order)
             return hipLaunchKernel(fn[which], grid, dim3(256), params, lds, s);
-        } else hipLaunchKernelGGL(gemm_f32_skinny_kernel, dim3(nwg, splits), dim3(256), 0, s, g2);
+        } else { report(RK_GEMM_SKINNY); hipLaunchKernelGGL(gemm_f32_skinny_kernel, dim3(nwg, splits), dim3(256), 0, s, g2); }
         return hipGetLastError();
     }
     if (g.split_k > 1) return hipErrorInvalidValue;  // split-K is only wired for the 64-tile form
@@ -973,7 +980,9 @@ inline hipError_t gemm_f32_launch(const GemmArgs &g, hipStream_t s)
             int gx = (Ni + 127) / 128, gy = (g.M + 127) / 128;
             const size_t lds = (size_t)(wide_floats<1>() + (fb == 1 ? wide_floats<1>() : wide_floats<2>())) * sizeof(float);
             void *params[3] = {const_cast<GemmArgs *>(&g), &gx, &gy};
-            hipError_t e = hipLaunchKernel(fn[fb == 2 ? 1 : plain_w ? (c_lines ? 3 : 2) : 0], dim3(std::min(gx * gy, wide_wgs)), dim3(256), params, lds, s);
+            const int which = fb == 2 ? 1 : plain_w ? (c_lines ? 3 : 2) : 0;
+            report(RK_GEMM_WIDE_11 + which);   // (RK_GEMM_WIDE_* are numbered in fn's order)
+            hipError_t e = hipLaunchKernel(fn[which], dim3(std::min(gx * gy, wide_wgs)), dim3(256), params, lds, s);
             if (e != hipSuccess) return e;
             if (Ni < g.N) {   // right strip: all rows, columns [Ni, N)
                 GemmArgs e1 = g;
@@ -981,7 +990,9 @@ inline hipError_t gemm_f32_launch(const GemmArgs &g, hipStream_t s)
                 if (g.col_bias) e1.col_bias = g.col_bias + Ni;
                 if (g.mask) e1.mask = g.mask + Ni;
                 if (g.acc_init) e1.acc_init = g.acc_init + Ni;
-                e = gemm_f32_launch(e1, s);
+                int strip_form[2];
+                e = gemm_f32_launch(e1, s, strip_form);
+                if (form_out) form_out[1] = strip_form[0];
                 if (e != hipSuccess) return e;
             }
             return hipSuccess;
@@ -996,9 +1007,9 @@ inline hipError_t gemm_f32_launch(const GemmArgs &g, hipStream_t s)
     // default: single LDS buffer + register prefetch, 3 workgroups per CU (measured 101 TF/s at K=256
     // vs 93 for the double-buffered 2-per-CU form, RK_GEMM_VARIANT=1)
     const bool plain = !g.row_bias && !g.col_bias && !g.relu && !g.mask && !g.sigmoid && !g.drop_thresh24;
-    if (g.a_ridx && plain && !g.acc_init) hipLaunchKernelGGL((gemm_f32_kernel<128, 1, 3, true, true>), grid, dim3(256), gemm_lds_bytes<128>(1), s, g, tpb);
-    else if (g.a_ridx || g.a_rmod) hipLaunchKernelGGL((gemm_f32_kernel<128, 1, 3, true, false>), grid, dim3(256), gemm_lds_bytes<128>(1), s, g, tpb);
-    else if (variant == 1) hipLaunchKernelGGL((gemm_f32_kernel<128, 2, 2>), grid, dim3(256), gemm_lds_bytes<128>(2), s, g, tpb);
-    else hipLaunchKernelGGL((gemm_f32_kernel<128, 1, 3>), grid, dim3(256), gemm_lds_bytes<128>(1), s, g, tpb);
+    if (g.a_ridx && plain && !g.acc_init) { report(RK_GEMM_TILE128_GATHER_PLAIN); hipLaunchKernelGGL((gemm_f32_kernel<128, 1, 3, true, true>), grid, dim3(256), gemm_lds_bytes<128>(1), s, g, tpb); }
+    else if (g.a_ridx || g.a_rmod) { report(RK_GEMM_TILE128_GATHER); hipLaunchKernelGGL((gemm_f32_kernel<128, 1, 3, true, false>), grid, dim3(256), gemm_lds_bytes<128>(1), s, g, tpb); }
+    else if (variant == 1) { report(RK_GEMM_TUNING_VARIANT); hipLaunchKernelGGL((gemm_f32_kernel<128, 2, 2>), grid, dim3(256), gemm_lds_bytes<128>(2), s, g, tpb); }
+    else { report(RK_GEMM_TILE128); hipLaunchKernelGGL((gemm_f32_kernel<128, 1, 3>), grid, dim3(256), gemm_lds_bytes<128>(1), s, g, tpb); }
     return hipGetLastError();
 }

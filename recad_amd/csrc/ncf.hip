@@ -7,14 +7,14 @@
 
 static int gemm(hipStream_t s, int M, int N, int K, const float *A, long long a_rs, long long a_cs, const float *B,
                 long long b_rs, long long b_cs, float *C, int ldc, const float *bias, int relu, const float *mask, int ldmask,
-                int split_k = 1)
+                int split_k = 1, int *form_out = nullptr)   // form_out: see gemm_f32_launch (rk_gemm_f32 only)
 {
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.split_k = split_k;
     g.M = M; g.N = N; g.K = K; g.A = A; g.a_rs = a_rs; g.a_cs = a_cs; g.B = B; g.b_rs = b_rs; g.b_cs = b_cs;
     g.C = C; g.ldc = ldc; g.col_bias = bias; g.relu = relu; g.mask = mask; g.ldmask = ldmask;
-    RK_HIP(gemm_f32_launch(g, s));
+    RK_HIP(gemm_f32_launch(g, s, form_out));
     return RK_OK;
 }
 
@@ -77,16 +77,17 @@ __global__ void slices_epilogue_kernel(long long n4, int N, int sp, const float 
 // 4e-4 differences on a third of MLP_layers.1.weight; with the dX GEMMs split only: 0 of 14.
 static int gemm_auto(hipStream_t s, int M, int N, int K, const float *A, long long a_rs, long long a_cs, const float *B,
                      long long b_rs, long long b_cs, float *C, const float *bias, int relu, const float *mask,
-                     float *scratch, long long cap_floats)
+                     float *scratch, long long cap_floats, int *form_out = nullptr, int *splits_out = nullptr)   // (reports: rk_gemm_f32 only)
 {
     const int sp = (N % 4 == 0 && scratch) ? pick_splits(M, N, K, cap_floats) : 1;
-    if (sp <= 1) return gemm(s, M, N, K, A, a_rs, a_cs, B, b_rs, b_cs, C, N, bias, relu, mask, N);
+    if (splits_out) *splits_out = sp <= 1 ? 1 : sp;
+    if (sp <= 1) return gemm(s, M, N, K, A, a_rs, a_cs, B, b_rs, b_cs, C, N, bias, relu, mask, N, 1, form_out);
     GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.split_k = sp; g.sk_part = scratch; g.sk_stride = (long long)M * N;
     g.M = M; g.N = N; g.K = K; g.A = A; g.a_rs = a_rs; g.a_cs = a_cs; g.B = B; g.b_rs = b_rs; g.b_cs = b_cs;
     g.C = C; g.ldc = N;
-    RK_HIP(gemm_f32_launch(g, s));
+    RK_HIP(gemm_f32_launch(g, s, form_out));
     const long long n4 = (long long)M * N / 4;
     hipLaunchKernelGGL(slices_epilogue_kernel, dim3((int)std::min<long long>((n4 + 255) / 256, 2048)), dim3(256), 0, s, n4, N, sp,
                        scratch, C, bias, relu, mask, 0);
@@ -105,7 +106,7 @@ static int gemm_auto(hipStream_t s, int M, int N, int K, const float *A, long lo
 static constexpr int kFwdBlocks = 8;
 static inline bool fwd_blocked(int K) { return K % 256 == 0; }
 static int gemm_fwd_blocked(hipStream_t s, int M, int N, int K, const float *A, const float *W, float *Y, const float *bias,
-                            float *scratch, long long cap_floats)
+                            float *scratch, long long cap_floats, int *form_out = nullptr)   // (report: rk_gemm_f32 only)
 {
     if (!scratch || cap_floats < (long long)kFwdBlocks * 64 * N || N % 4) RK_FAIL(RK_EINVAL, "ncf: the blocked forward needs desc.gemm_scratch of >= %lld floats", (long long)kFwdBlocks * 64 * N);
     const int rows_cap = (int)std::min<long long>(M, cap_floats / ((long long)kFwdBlocks * N) / 64 * 64);
@@ -116,12 +117,73 @@ static int gemm_fwd_blocked(hipStream_t s, int M, int N, int K, const float *A, 
         g.split_k = kFwdBlocks; g.sk_part = scratch; g.sk_stride = (long long)mc * N;
         g.M = mc; g.N = N; g.K = K; g.A = A + (size_t)m0 * K; g.a_rs = K; g.a_cs = 1; g.B = W; g.b_rs = K; g.b_cs = 1;
         g.C = Y + (size_t)m0 * N; g.ldc = N;
-        RK_HIP(gemm_f32_launch(g, s));
+        RK_HIP(gemm_f32_launch(g, s, form_out));
         const long long n4 = (long long)mc * N / 4;
         hipLaunchKernelGGL(slices_epilogue_kernel, dim3((int)std::min<long long>((n4 + 255) / 256, 2048)), dim3(256), 0, s, n4, N, kFwdBlocks,
                            scratch, Y + (size_t)m0 * N, bias, 1, (const float *)nullptr, 1);
         RK_CHECK_LAUNCH();
     }
+    return RK_OK;
+}
+
+// TEST AND DIAGNOSTIC ENTRY (include/recad_hip.h): one GEMM through gemm_f32_launch or one of the two host policies above, with
+// the form and the K-slices they chose reported.  It lives in this file so that what it launches are the kernels, the
+// dispatcher and the policies the tower launches.  Everything a kernel takes on trust from its callers is checked here.
+RK_EXPORT int rk_gemm_f32(const rk_gemm_desc *desc, int32_t *form_out, int32_t *splits_out, void *stream)
+{
+    if (!desc) RK_FAIL(RK_EINVAL, "rk_gemm_f32: desc is NULL");
+    const rk_gemm_desc &d = *desc;
+    hipStream_t s = (hipStream_t)stream;
+    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || !d.A || !d.B || !d.C) RK_FAIL(RK_EINVAL, "rk_gemm_f32: sizes must be positive and A, B, C given");
+    if (d.ldc < d.N || (d.mask && d.ldmask < d.N)) RK_FAIL(RK_EINVAL, "rk_gemm_f32: ldc / ldmask below N");
+    if (d.row_bias && !d.col_bias) RK_FAIL(RK_EINVAL, "rk_gemm_f32: row_bias needs col_bias");
+    if (d.a_rmod < 0 || d.a_roff < 0) RK_FAIL(RK_EINVAL, "rk_gemm_f32: a_rmod / a_roff negative");
+    if (d.acc_init && (d.a_rmod <= 0 || d.a_ridx || d.ld_init < d.N || d.a_roff / d.a_rmod < d.init_base))
+        RK_FAIL(RK_EINVAL, "rk_gemm_f32: acc_init needs a_rmod > 0 without a_ridx, ld_init >= N and init_base <= a_roff / a_rmod");
+    if (d.drop_thresh24 > (1u << 24)) RK_FAIL(RK_EINVAL, "rk_gemm_f32: drop_thresh24 above 2^24");
+    if ((long long)d.M * d.N > 0xFFFFFFFFLL && d.drop_thresh24) RK_FAIL(RK_EINVAL, "rk_gemm_f32: dropout counters are 32-bit");
+    const bool epilogue = d.col_bias || d.row_bias || d.const_add != 0.f || d.relu || d.sigmoid || d.drop_thresh24 || d.mask;
+    int form[2] = {RK_GEMM_FORM_NONE, RK_GEMM_FORM_NONE}, splits = 1, rc = RK_OK;
+    if (d.policy == RK_GEMM_POLICY_LAUNCH) {
+        if (d.split_k > 1) {
+            if (epilogue || d.acc_init || d.a_ridx || d.a_rmod) RK_FAIL(RK_EINVAL, "rk_gemm_f32: split_k takes no epilogue, prefix or gather");
+            // slice q's partial of C(m, n) is parked at sk_part[q * sk_stride + m * ldc + n]: slices must not overlap
+            if (d.sk_part && d.sk_stride < (long long)(d.M - 1) * d.ldc + d.N) RK_FAIL(RK_EINVAL, "rk_gemm_f32: sk_stride below (M - 1) * ldc + N");
+            const long long nwg128 = (long long)((d.N + 127) / 128) * ((d.M + 127) / 128);
+            if (!d.sk_part && nwg128 >= 384) RK_FAIL(RK_EINVAL, "rk_gemm_f32: split_k by atomics is wired for fewer than 384 128-tiles only");
+        }
+        GemmArgs g;
+        memset(&g, 0, sizeof(g));
+        g.M = d.M; g.N = d.N; g.K = d.K; g.A = d.A; g.a_rs = d.a_rs; g.a_cs = d.a_cs; g.a_ridx = d.a_ridx; g.a_rmod = d.a_rmod; g.a_roff = d.a_roff;
+        g.acc_init = d.acc_init; g.ld_init = d.ld_init; g.init_base = d.init_base; g.B = d.B; g.b_rs = d.b_rs; g.b_cs = d.b_cs;
+        g.C = d.C; g.ldc = d.ldc; g.col_bias = d.col_bias; g.row_bias = d.row_bias; g.const_add = d.const_add; g.relu = d.relu;
+        g.sigmoid = d.sigmoid; g.drop_thresh24 = d.drop_thresh24; g.drop_scale = d.drop_scale; g.drop_seed = d.drop_seed;
+        g.mask = d.mask; g.ldmask = d.ldmask; g.sk_part = d.split_k > 1 ? d.sk_part : nullptr; g.sk_stride = d.sk_stride; g.split_k = d.split_k;
+        hipError_t e = gemm_f32_launch(g, s, form);
+        if (e != hipSuccess) RK_FAIL(RK_EHIP, "rk_gemm_f32: gemm_f32_launch failed: %s", hipGetErrorString(e));
+        // (only the 64-tile forms slice K; they launch gemm_effective_splits slices)
+        splits = form[0] >= RK_GEMM_SKINNY && form[0] <= RK_GEMM_DEEP_22_32 ? gemm_effective_splits(d.K, d.split_k) : 1;
+    } else if (d.policy == RK_GEMM_POLICY_AUTO || d.policy == RK_GEMM_POLICY_FWD_BLOCKED) {
+        if (d.a_ridx || d.a_rmod || d.acc_init || d.row_bias || d.const_add != 0.f || d.sigmoid || d.drop_thresh24 || d.split_k > 1 || d.sk_part)
+            RK_FAIL(RK_EINVAL, "rk_gemm_f32: policies 1 and 2 take col_bias, relu and mask only");
+        if (d.ldc != d.N || (d.mask && d.ldmask != d.N)) RK_FAIL(RK_EINVAL, "rk_gemm_f32: policies 1 and 2 need contiguous C and mask");
+        if (d.scratch && (d.scratch_floats <= 0 || ((uintptr_t)d.scratch & 15) != 0)) RK_FAIL(RK_EINVAL, "rk_gemm_f32: scratch must be 16-byte aligned and sized");
+        // the slice-adding pass moves float4s
+        if (d.scratch && (((uintptr_t)d.C & 15) != 0 || ((uintptr_t)d.col_bias & 15) != 0 || ((uintptr_t)d.mask & 15) != 0))
+            RK_FAIL(RK_EINVAL, "rk_gemm_f32: policies 1 and 2 need 16-byte aligned C, col_bias and mask");
+        if (d.policy == RK_GEMM_POLICY_AUTO) {
+            rc = gemm_auto(s, d.M, d.N, d.K, d.A, d.a_rs, d.a_cs, d.B, d.b_rs, d.b_cs, d.C, d.col_bias, d.relu, d.mask, d.scratch,
+                           d.scratch ? d.scratch_floats : 0, form, &splits);
+        } else {
+            if (!fwd_blocked(d.K) || d.a_rs != d.K || d.a_cs != 1 || d.b_rs != d.K || d.b_cs != 1 || !d.relu || d.mask)
+                RK_FAIL(RK_EINVAL, "rk_gemm_f32: policy 2 needs K %% 256 == 0, dense k-contiguous A and B, relu and no mask");
+            rc = gemm_fwd_blocked(s, d.M, d.N, d.K, d.A, d.B, d.C, d.col_bias, d.scratch, d.scratch ? d.scratch_floats : 0, form);
+            splits = kFwdBlocks;
+        }
+    } else RK_FAIL(RK_EINVAL, "rk_gemm_f32: unknown policy %d", d.policy);
+    if (rc != RK_OK) return rc;
+    if (form_out) { form_out[0] = form[0]; form_out[1] = form[1]; }
+    if (splits_out) *splits_out = splits;
     return RK_OK;
 }
 

@@ -6,6 +6,7 @@ import torch
 
 from oracle import oracle as orc
 from tests import _golden as G
+from tests._drop_restate import _drop_keep, _mix64, _step_seed
 from tests._stub import LGN_KEYS, PW_KEYS, ReplayDataset
 
 pytestmark = pytest.mark.gpu
@@ -1588,15 +1589,6 @@ def test_lightgcn_deterministic_scatter(gpu_device, d, L, graph_steps, lds):
     assert G.relerr(m.embedding_item.weight.detach().cpu().numpy(), i0) < TABLE_RTOL
 
 
-def _mix64(z):
-    """numpy mirror of rk_mix64 (recad_amd/csrc/common.h), uint64 wrap-around arithmetic"""
-    with np.errstate(over="ignore"):
-        z = (np.asarray(z, dtype=np.uint64) + np.uint64(0x9E3779B97F4A7C15))
-        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-        return z ^ (z >> np.uint64(31))
-
-
 def _dropout_mask(base_seed, step, nnz, keep_prob):
     """keep[e] of rk_drop_keep for every stored entry e under the step's seed (common.h)"""
     with np.errstate(over="ignore"):
@@ -2526,19 +2518,6 @@ def test_mf_full_size_ml1m(gpu_device):
     rank = got["target_rank"].cpu().numpy()[sel, 0]
     for i, k in enumerate([10, 20, 50, 100]):
         assert np.array_equal((rank < k).astype(np.float64), rows[:, 2 + i])
-
-
-def _drop_keep(seed_step, n, keep_prob):
-    """numpy mirror of rk_drop_keep (recad_amd/csrc/common.h) for element ids 0..n-1"""
-    with np.errstate(over="ignore"):
-        ids = np.arange(n, dtype=np.uint64) * np.uint64(0xD1342543DE82EF95)
-        u24 = _mix64(np.uint64(seed_step) ^ ids) >> np.uint64(40)
-    return u24 < np.uint64(int((1.0 - (1.0 - float(keep_prob))) * 16777216.0))
-
-
-def _step_seed(base, step):
-    with np.errstate(over="ignore"):
-        return int(_mix64(np.uint64(base) ^ _mix64(np.uint64(step))))
 
 
 def _torch_ncf(params, mode, f, L, users, items, drop=None):

@@ -25,7 +25,7 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/recad_hip.h but not exported"
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
-    assert _lib.lib().rk_abi_version() == _lib.ABI_VERSION == 9
+    assert _lib.lib().rk_abi_version() == _lib.ABI_VERSION == 10
 
 
 def test_no_cpu_fallback():
@@ -322,6 +322,9 @@ def test_ctypes_descriptors_match_the_header(tmp_path):
         "rk_ncf_desc": ["n_users", "lr", "ug", "pw", "grad", "m", "v", "acts", "d0", "max_batch", "gemm_scratch",
                         "gemm_scratch_floats", "wgrad_part"],
         "rk_spmm_epilogue": [],
+        "rk_gemm_desc": ["M", "policy", "A", "a_cs", "a_ridx", "a_rmod", "a_roff", "acc_init", "ld_init", "init_base", "B", "b_cs", "C",
+                         "ldc", "col_bias", "row_bias", "const_add", "relu", "sigmoid", "drop_thresh24", "drop_scale", "drop_seed",
+                         "mask", "ldmask", "sk_part", "sk_stride", "split_k", "scratch", "scratch_floats"],
     }
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "recad_hip.h"', 'int main(void) {']
     for st, fields in probes.items():
@@ -335,7 +338,8 @@ def test_ctypes_descriptors_match_the_header(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     subprocess.run(["gcc", "-I", os.path.join(root, "include"), str(src), "-o", str(exe)], check=True)
     out = dict(l.split() for l in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
-    mirrors = {"rk_lightgcn_desc": _lib.LightGCNDesc, "rk_ncf_desc": _lib.NCFDesc, "rk_spmm_epilogue": _lib.SpmmEpilogue}
+    mirrors = {"rk_lightgcn_desc": _lib.LightGCNDesc, "rk_ncf_desc": _lib.NCFDesc, "rk_spmm_epilogue": _lib.SpmmEpilogue,
+               "rk_gemm_desc": _lib.GemmDesc}
     rename = {"lambda": "lam"}
     for st, fields in probes.items():
         cls = mirrors[st]
