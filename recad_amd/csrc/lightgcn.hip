@@ -272,8 +272,10 @@ __global__ __launch_bounds__(kRowsWaves * 64) void bpr_rows_kernel(const BprArgs
                 for (int o = kRowsGL / 2; o > 0; o >>= 1) { ps += __shfl_xor(ps, o, 64); ns += __shfl_xor(ns, o, 64); }
                 const float x = ns - ps;
                 const float dx = (x > 20.f ? 1.f : 1.f / (1.f + expf(-x))) * invB * inv_layers;
+                // (the node rows are fetched by the whole wave: inside the branch below lane `src` may be switched off -- from round 16 on it
+                //  belongs to a group past the run's end -- and a shuffle from an inactive lane reads 0, i.e. node row 0's embedding)
+                const int nu = DIRECT ? __shfl(iu, src, 64) : ru, np_ = DIRECT ? __shfl(ip, src, 64) : rp, nn = DIRECT ? __shfl(in_, src, 64) : rn;
                 if (live && ro == 0) {   // this triplet's loss terms, once
-                    const int nu = DIRECT ? __shfl(iu, src, 64) : ru, np_ = DIRECT ? __shfl(ip, src, 64) : rp, nn = DIRECT ? __shfl(in_, src, 64) : rn;
                     float rr = 0.f;
                     if (vec4) {   // (four consecutive columns from a multiple of 4 are contiguous in the sliced layout too)
                         for (int k = l4 * 4; k < d; k += kRowsGL * 4) {

@@ -6,6 +6,7 @@ import torch
 
 from oracle import oracle as orc
 from tests import _golden as G
+from tests._csr_rand import _rand_csr
 from tests._drop_restate import _drop_keep, _mix64, _step_seed
 from tests._stub import LGN_KEYS, PW_KEYS, ReplayDataset
 
@@ -13,18 +14,6 @@ pytestmark = pytest.mark.gpu
 
 LOSS_RTOL = 1e-5
 TABLE_RTOL = 1e-4
-
-
-def _rand_csr(rng, n, avg, long_rows=()):
-    deg = rng.poisson(avg, n).astype(np.int64)
-    for r, k in long_rows:
-        deg[r] = k
-    deg = np.minimum(deg, n)
-    rowptr = np.zeros(n + 1, dtype=np.int32)
-    rowptr[1:] = np.cumsum(deg)
-    col = np.concatenate([np.sort(rng.choice(n, size=k, replace=False)) for k in deg]).astype(np.int32)
-    val = rng.random(len(col), dtype=np.float32)
-    return rowptr, col, val
 
 
 @pytest.mark.parametrize("d", [32, 64, 128, 256, 48, 100])
