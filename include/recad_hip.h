@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define RK_ABI_VERSION 10
+#define RK_ABI_VERSION 11
 #define RK_OK 0
 #define RK_EINVAL (-22)   /* bad argument / unsupported shape */
 #define RK_EHIP (-5)      /* a HIP runtime call failed */
@@ -141,6 +141,14 @@ int rk_lds_plan_build(int32_t n_users, int32_t n_items, const int32_t *rowptr, c
 /* the same from HOST arrays, no HIP call (n_cu = compute units to fill): what the CPU tests drive */
 int rk_lds_plan_build_host(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
                            int32_t dim, int32_t n_cu, rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info);
+/* the same with the plan's FORM asked for (ABI 11): slice_items / slice_users = slice width in floats of the items / users table
+ * (0 = choose, 4, 8, 16: lpa / lpb = 1, 2, 4 lanes per entry), chunk_cap = 0 (choose), 64, 96, 128, 256, 512; any other value is
+ * RK_EINVAL.  A width that does not divide dim, or a form that does not fit a CU's LDS, gives *n_words == 0 like a graph that
+ * does not qualify.  All zero = rk_lds_plan_build_host, word for word.  The shipped planner only ever picks one form; this entry
+ * is how the tests reach every instantiation rk_spmm_lds dispatches to (lpa, lpb: (1,1) (1,2) (2,1) (2,2) (4,4) (4,2) (2,4)). */
+int rk_lds_plan_build_host_ex(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
+                              int32_t dim, int32_t n_cu, int32_t slice_items, int32_t slice_users, int32_t chunk_cap,
+                              rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info);
 int rk_lds_plan_words(rk_lds_plan_t plan, int32_t *host_out /*[n_words]*/);
 int rk_lds_plan_upload(rk_lds_plan_t plan, int32_t *dev /*[n_words], 16-byte aligned*/, void *stream);
 int rk_lds_plan_destroy(rk_lds_plan_t plan);

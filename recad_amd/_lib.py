@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librecad_hip.so")
 RK_LOSS_PARTIALS = 256
 RK_MAX_GRAPH_STEPS = 64
-ABI_VERSION = 10
+ABI_VERSION = 11
 RK_LDS_SYNC_WORDS = 2560
 RK_PCA_GRAM_BLOCKS = 256
 RK_RANK_MAX_NK = 8   # cut-offs per rk_rank_metrics call
@@ -198,6 +198,7 @@ _SIGNATURES = {
     "rk_spmm_csr_ex": [_I32, _P, _P, _P, _P, _I32, _P, _I32, _P, _I64, C.POINTER(SpmmEpilogue), _P],
     "rk_lds_plan_build": [_I32, _I32, _P, _P, _P, _I32, _P, C.POINTER(_P), C.POINTER(_I64), C.POINTER(LdsInfo)],
     "rk_lds_plan_build_host": [_I32, _I32, _P, _P, _P, _I32, _I32, C.POINTER(_P), C.POINTER(_I64), C.POINTER(LdsInfo)],
+    "rk_lds_plan_build_host_ex": [_I32, _I32, _P, _P, _P, _I32, _I32, _I32, _I32, _I32, C.POINTER(_P), C.POINTER(_I64), C.POINTER(LdsInfo)],
     "rk_lds_plan_words": [_P, _P],
     "rk_lds_plan_upload": [_P, _P, _P],
     "rk_lds_plan_destroy": [_P],

@@ -219,11 +219,12 @@ static bool choose_half(const int32_t *rp, int row_lo, int row_hi, int n_src, in
 {
     // 4-float slices first: one lane per entry lets the kernel form an LDS address with one SDWA shift; 8-float slices
     // (two lanes per entry, half the stream traffic) measured the same before that and are kept as RK_LDS_SA/SB=8
-    static const int kS[] = {4, 8};
+    // 16-float slices (four lanes per entry) are only ever taken when asked for (rk_lds_plan_build_host_ex)
+    static const int kS[] = {4, 8, 16};
     static const int kC[] = {64, 96, 128, 256, 512};   // 64: 10.8 us per ml1m launch against 12.1 (32) and 11.4 (128)
     const int limit = kLdsMaxBytes - 256;
     for (int S : kS) {
-        if (force_s && S != force_s) continue;
+        if (force_s ? S != force_s : S == 16) continue;
         if (dim % S) continue;
         const int n_slices = dim / S;
         int n_blk = std::max(1, n_cu_half / n_slices);
@@ -253,16 +254,20 @@ using namespace rk_plan_detail;
 
 // Host-only builder (no HIP call): every array is host memory.  *n_words == 0 on return: the graph does not qualify
 // (not bipartite / not the normalised binary adjacency / a class table does not fit a CU's LDS) -- use spmm.h's kernel.
+// slice_items / slice_users / chunk_cap: 0 = choose (the shipped plans), else the slice width of the items / users table in
+// floats and the chunk cap the plan must have (rk_lds_plan_build_host_ex: how the tests reach every kernel form)
 inline int lds_plan_build_host_body(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
-                                    int32_t dim, int32_t n_cu, rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info);
+                                    int32_t dim, int32_t n_cu, int32_t slice_items, int32_t slice_users, int32_t chunk_cap,
+                                    rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info);
 // The C-ABI entry points call THIS: no C++ exception (std::bad_alloc of a builder vector, std::system_error of the thread
 // pool) may unwind through extern "C" -- the perturb-retrain loop calls the builder once per injected graph, and a transient
 // resource limit must come back as RK_E*, not std::terminate.
 inline int lds_plan_build_host_impl(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
-                                    int32_t dim, int32_t n_cu, rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info)
+                                    int32_t dim, int32_t n_cu, rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info,
+                                    int32_t slice_items = 0, int32_t slice_users = 0, int32_t chunk_cap = 0)
 {
     try {
-        return lds_plan_build_host_body(n_users, n_items, rowptr, col, val, dim, n_cu, out, n_words, info);
+        return lds_plan_build_host_body(n_users, n_items, rowptr, col, val, dim, n_cu, slice_items, slice_users, chunk_cap, out, n_words, info);
     } catch (const std::bad_alloc &) {
         if (out) *out = nullptr;
         if (n_words) *n_words = 0;
@@ -274,10 +279,15 @@ inline int lds_plan_build_host_impl(int32_t n_users, int32_t n_items, const int3
     }
 }
 inline int lds_plan_build_host_body(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
-                                    int32_t dim, int32_t n_cu, rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info)
+                                    int32_t dim, int32_t n_cu, int32_t slice_items, int32_t slice_users, int32_t chunk_cap,
+                                    rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info)
 {
     if (n_users <= 0 || n_items <= 0 || !rowptr || !col || dim <= 0 || !out || !n_words || !info)
         RK_FAIL(RK_EINVAL, "rk_lds_plan_build_host: bad arguments");
+    for (int32_t sw : {slice_items, slice_users})
+        if (sw != 0 && sw != 4 && sw != 8 && sw != 16) RK_FAIL(RK_EINVAL, "rk_lds_plan_build_host_ex: a slice width is 0 (choose), 4, 8 or 16 floats, not %d", (int)sw);
+    if (chunk_cap != 0 && chunk_cap != 64 && chunk_cap != 96 && chunk_cap != 128 && chunk_cap != 256 && chunk_cap != 512)
+        RK_FAIL(RK_EINVAL, "rk_lds_plan_build_host_ex: a chunk cap is 0 (choose), 64, 96, 128, 256 or 512, not %d", (int)chunk_cap);
     *out = nullptr;
     *n_words = 0;
     memset(info, 0, sizeof(*info));
@@ -303,9 +313,11 @@ inline int lds_plan_build_host_body(int32_t n_users, int32_t n_items, const int3
             }
         }
     }
-    static const int force_sa = RK_TUNE_INT("RK_LDS_SA", 0);   // tuning: slice width of the items table
-    static const int force_sb = RK_TUNE_INT("RK_LDS_SB", 0);   // ... of the users table
-    static const int force_c = RK_TUNE_INT("RK_LDS_CHUNK", 0);
+    static const int tune_sa = RK_TUNE_INT("RK_LDS_SA", 0);   // tuning: slice width of the items table
+    static const int tune_sb = RK_TUNE_INT("RK_LDS_SB", 0);   // ... of the users table
+    static const int tune_c = RK_TUNE_INT("RK_LDS_CHUNK", 0);
+    const int force_sa = slice_items ? slice_items : tune_sa, force_sb = slice_users ? slice_users : tune_sb;
+    const int force_c = chunk_cap ? chunk_cap : tune_c;
     HalfPlan hp[2];
     // half 0: user rows gather the items table; half 1: item rows gather the users table
     if (!choose_half(rp, 0, U, I, dim, n_cu / 2, force_sa, force_c, &hp[0])) return RK_OK;

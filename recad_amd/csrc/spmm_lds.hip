@@ -12,6 +12,13 @@ RK_EXPORT int rk_lds_plan_build_host(int32_t n_users, int32_t n_items, const int
     return lds_plan_build_host_impl(n_users, n_items, rowptr, col, val, dim, n_cu, out, n_words, info);
 }
 
+RK_EXPORT int rk_lds_plan_build_host_ex(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
+                                        int32_t dim, int32_t n_cu, int32_t slice_items, int32_t slice_users, int32_t chunk_cap,
+                                        rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info)
+{
+    return lds_plan_build_host_impl(n_users, n_items, rowptr, col, val, dim, n_cu, out, n_words, info, slice_items, slice_users, chunk_cap);
+}
+
 RK_EXPORT int rk_lds_plan_build(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
                                 int32_t dim, void *stream, rk_lds_plan_t *out, int64_t *n_words, rk_lds_info *info)
 {
@@ -109,6 +116,7 @@ RK_EXPORT int rk_spmm_lds(const rk_lds_info *info, const int32_t *plan, const fl
     int rc = lds_info_of(info, &li, "rk_spmm_lds");
     if (rc) return rc;
     if (!plan || !x || !epi) RK_FAIL(RK_EINVAL, "rk_spmm_lds: bad arguments");
+    if (reinterpret_cast<uintptr_t>(plan) & 15) RK_FAIL(RK_EINVAL, "rk_spmm_lds: the plan must be 16-byte aligned (rk_lds_plan_upload)");   // (its records and stream are read with 16-byte loads)
     if (epi->sum_out && !epi->sum_in) RK_FAIL(RK_EINVAL, "rk_spmm_lds: sum_out needs sum_in");
     hipStream_t s = (hipStream_t)stream;
     LdsArgs a;

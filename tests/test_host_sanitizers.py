@@ -1,7 +1,8 @@
 """The HOST-ONLY builders (recad_amd/csrc/host/*.h: the LDS plan builder with its std::thread pool, the CSR schedule builder)
 under AddressSanitizer + UBSan and under ThreadSanitizer (CPU builds only): `make -C recad_amd/csrc host-asan
 host-tsan` compiles tests/tools/host_builders_driver.cpp, which runs both builders on a stress set of graphs from several
-caller threads at once.  Both runs must be clean AND produce the product library's words bit for bit."""
+caller threads at once -- a dozen of them with the plan's FORM forced (slice widths up to 16, chunk caps up to 512: the builder's
+paths the shipped choice never takes).  Both runs must be clean AND produce the product library's words bit for bit."""
 import ctypes as C
 import os
 import subprocess
@@ -10,14 +11,15 @@ import numpy as np
 import pytest
 
 from recad_amd import _lib, synth
-from tests.test_lds_plan_cpu import norm_adj_csr
+from tests import _lds_restate as R
+from tests._lds_restate import norm_adj_csr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "recad_amd", "csrc")
 
 
 def _graphs():
-    """(U, I, dim, n_cu, split, rowptr, col, val): the reference-shaped graphs + the randomised family of
+    """(U, I, dim, n_cu, split, rowptr, col, val[, (slice_items, slice_users, chunk_cap)]): the reference-shaped graphs + the randomised family of
     tests/tools/spmm_lds_stress.py (tiny classes, empty rows, full rows, dense and sparse; every dim % 4 == 0 up to 256)."""
     out = []
     for shape, dims in (("tiny", (16, 32, 64, 128, 256)), ("ml1m", (64,))):
@@ -44,17 +46,34 @@ def _graphs():
         idx = np.concatenate([np.sort(rng.choice(I, size=int(k), replace=False)) for k in deg]).astype(np.int32)
         rp, col, val = norm_adj_csr(U, I, ptr, idx)
         out.append((U, I, d, int(rng.choice([8, 64, 256])), int(rng.integers(0, 2)), rp, col, val))
+    # forced forms (rk_lds_plan_build_host_ex): every width and cap, on the graphs of tests/test_spmm_lds_forms_*.py
+    for name, d, n_cu, force in (("edge", 16, 8, (16, 16, 512)), ("edge", 48, 256, (16, 8, 0)), ("edge_t", 16, 2, (8, 16, 96)), ("edge_t", 48, 8, (8, 8, 128)),
+                                 ("edge", 16, 256, (4, 8, 64)), ("edge_t", 16, 8, (8, 4, 256)), ("tall", 16, 2, (4, 4, 512)), ("long2", 8, 256, (4, 8, 0)),
+                                 ("long4", 16, 2, (16, 16, 256)), ("three", 16, 8, (4, 16, 0)), ("one", 16, 8, (16, 16, 0)), ("edge", 12, 8, (8, 4, 0)),
+                                 ("tiny", 64, 64, (16, 16, 512)), ("tiny", 64, 256, (0, 8, 96))):
+        if name == "tiny":
+            data = synth.make("tiny")
+            U, I = data["n_users"], data["n_items"]
+            rp, col, val = norm_adj_csr(U, I, *data["train"])
+        else:
+            U, I, rp, col, val = R.graph(name)
+        out.append((U, I, d, n_cu, 1, rp, col, val, force))
     return out
 
 
 def _product_words(g):
     """the shipped library's builders on the same graph (pure host entry points: no GPU needed)"""
-    U, I, d, n_cu, split, rp, col, val = g
+    U, I, d, n_cu, split, rp, col, val = g[:8]
+    force = g[8] if len(g) > 8 else None
     L = _lib.lib()
     rp_, col_, val_ = (np.ascontiguousarray(a) for a in (rp.astype(np.int32), col.astype(np.int32), val.astype(np.float32)))
     plan, n_words, info = C.c_void_p(), C.c_int64(0), _lib.LdsInfo()
-    _lib.check(L.rk_lds_plan_build_host(U, I, rp_.ctypes.data_as(C.c_void_p), col_.ctypes.data_as(C.c_void_p), val_.ctypes.data_as(C.c_void_p),
-                                        d, n_cu, C.byref(plan), C.byref(n_words), C.byref(info)), "rk_lds_plan_build_host")
+    if force is None:
+        _lib.check(L.rk_lds_plan_build_host(U, I, rp_.ctypes.data_as(C.c_void_p), col_.ctypes.data_as(C.c_void_p), val_.ctypes.data_as(C.c_void_p),
+                                            d, n_cu, C.byref(plan), C.byref(n_words), C.byref(info)), "rk_lds_plan_build_host")
+    else:
+        _lib.check(L.rk_lds_plan_build_host_ex(U, I, rp_.ctypes.data_as(C.c_void_p), col_.ctypes.data_as(C.c_void_p), val_.ctypes.data_as(C.c_void_p),
+                                               d, n_cu, *force, C.byref(plan), C.byref(n_words), C.byref(info)), "rk_lds_plan_build_host_ex")
     pw = np.zeros(n_words.value, dtype=np.int32)
     if n_words.value:
         _lib.check(L.rk_lds_plan_words(plan, pw.ctypes.data_as(C.c_void_p)), "rk_lds_plan_words")
@@ -74,8 +93,9 @@ def stress_set(tmp_path_factory):
     path = str(tmp_path_factory.mktemp("hostsan") / "graphs.bin")
     with open(path, "wb") as f:
         f.write(np.int32(len(gs)).tobytes())
-        for U, I, d, n_cu, split, rp, col, val in gs:
-            f.write(np.asarray([U, I, d, n_cu, split, len(col)], dtype=np.int32).tobytes())
+        for g in gs:
+            U, I, d, n_cu, split, rp, col, val = g[:8]
+            f.write(np.asarray([U, I, d, n_cu, split, len(col), *(g[8] if len(g) > 8 else (0, 0, 0))], dtype=np.int32).tobytes())
             f.write(rp.astype(np.int32).tobytes()); f.write(col.astype(np.int32).tobytes()); f.write(val.astype(np.float32).tobytes())
     return gs, path, [_product_words(g) for g in gs]
 
@@ -109,4 +129,6 @@ def test_host_builders_under_sanitizers(san, stress_set, tmp_path):
         got = np.frombuffer(buf[o:o + 4 * nsw], dtype=np.int32); o += 4 * nsw
         assert nb == n_blocks and sc == scr and np.array_equal(got, sw), ("schedule differs", g[:5])
         n_plans += npw > 0
+    n_forced = sum(1 for g, w in zip(gs, want) if len(g) > 8 and len(w[0]) > 0)
+    assert n_forced >= 12      # (edge at dim 12 with 8-float slices: refused by both, like any graph that does not qualify)
     assert o == len(buf) and n_plans >= 20     # (graphs whose tables do not fit a CU's LDS give no plan: still scheduled)

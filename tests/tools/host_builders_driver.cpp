@@ -3,7 +3,8 @@
 // like independent victims on their own streams would -- and writes the words they produce, which the test compares bit for bit
 // with the product library's.  Built by `make -C recad_amd/csrc host-asan host-tsan`; never part of librecad_hip.so.
 //
-// input file : int32 n_graphs, then per graph: int32 U, I, dim, n_cu, class_split_flag, nnz; int32 rowptr[U+I+1]; int32 col[nnz]; float val[nnz]
+// input file : int32 n_graphs, then per graph: int32 U, I, dim, n_cu, class_split_flag, nnz, slice_items, slice_users, chunk_cap (the
+//              plan's form, 0 = choose: rk_lds_plan_build_host_ex); int32 rowptr[U+I+1]; int32 col[nnz]; float val[nnz]
 // output file: per graph: int64 n_plan_words, int32 plan_words[...], int64 n_sched_words, int32 n_blocks, int64 scratch_words, int32 sched_words[...]
 #include <stdio.h>
 
@@ -16,7 +17,7 @@
 thread_local char rk_err_buf[512] = "";
 
 struct Graph {
-    int32_t U, I, dim, n_cu, split, nnz;
+    int32_t U, I, dim, n_cu, split, nnz, slice_items, slice_users, chunk_cap;
     std::vector<int32_t> rowptr, col;
     std::vector<float> val;
     std::vector<int32_t> plan, sched;
@@ -32,7 +33,8 @@ static void run_one(Graph &g)
     rk_lds_plan_t plan = nullptr;
     int64_t n_words = 0;
     rk_lds_info info;
-    g.rc = lds_plan_build_host_impl(g.U, g.I, g.rowptr.data(), g.col.data(), g.val.data(), g.dim, g.n_cu, &plan, &n_words, &info);
+    g.rc = lds_plan_build_host_impl(g.U, g.I, g.rowptr.data(), g.col.data(), g.val.data(), g.dim, g.n_cu, &plan, &n_words, &info,
+                                    g.slice_items, g.slice_users, g.chunk_cap);
     if (g.rc) return;
     if (plan) {
         g.plan = plan->words;
@@ -62,9 +64,10 @@ int main(int argc, char **argv)
     if (!read_all(f, &n, 4) || n <= 0 || n > 100000) { fprintf(stderr, "bad header\n"); return 2; }
     std::vector<Graph> gs((size_t)n);
     for (Graph &g : gs) {
-        int32_t h[6];
+        int32_t h[9];
         if (!read_all(f, h, sizeof(h))) { fprintf(stderr, "truncated input\n"); return 2; }
         g.U = h[0]; g.I = h[1]; g.dim = h[2]; g.n_cu = h[3]; g.split = h[4]; g.nnz = h[5];
+        g.slice_items = h[6]; g.slice_users = h[7]; g.chunk_cap = h[8];
         g.rowptr.resize((size_t)g.U + g.I + 1); g.col.resize((size_t)g.nnz); g.val.resize((size_t)g.nnz);
         if (!read_all(f, g.rowptr.data(), 4 * g.rowptr.size()) || !read_all(f, g.col.data(), 4 * g.col.size()) || !read_all(f, g.val.data(), 4 * g.val.size())) {
             fprintf(stderr, "truncated input\n");
@@ -83,7 +86,7 @@ int main(int argc, char **argv)
     for (const Graph &g : gs) {
         if (g.rc) { fprintf(stderr, "builder failed: rc %d (%s)\n", g.rc, rk_err_buf); return 3; }
         const int64_t np = (int64_t)g.plan.size(), ns = (int64_t)g.sched.size();
-        fwrite(&np, 8, 1, o); fwrite(g.plan.data(), 4, g.plan.size(), o);
+        fwrite(&np, 8, 1, o); if (np) fwrite(g.plan.data(), 4, g.plan.size(), o);   // (a graph without a plan: no null pointer into fwrite)
         fwrite(&ns, 8, 1, o); fwrite(&g.n_blocks, 4, 1, o); fwrite(&g.scratch_words, 8, 1, o); fwrite(g.sched.data(), 4, g.sched.size(), o);
     }
     fclose(o);
