@@ -395,7 +395,9 @@ int rk_bpr_sample(int32_t n_users, int32_t n_items, const int32_t *pos_ptr, cons
 
 /* (user, item, label) rows of pointwise_sample, recad/dataset/implicit.py:77-91: each train edge
  * once with label 1, followed by negative_ratio rows with label 0 whose item is uniform (with
- * replacement) over the user's non-interacted items.  Outputs: int64[n_edges*(negative_ratio+1)]. */
+ * replacement) over the user's non-interacted items.  Outputs: int64[n_edges*(negative_ratio+1)].
+ * A user who has interacted with every item has no such item: its negative rows hold (user, item 0, label 0) and are
+ * the caller's to discard (ImplicitData._device_epoch does); the reference cannot draw one either. */
 int rk_pointwise_sample(int32_t n_users, int32_t n_items, const int32_t *train_ptr, const int32_t *train_idx,
                         int64_t n_edges, int32_t negative_ratio, uint64_t seed, int64_t *users, int64_t *items,
                         int64_t *labels, void *stream);

@@ -271,7 +271,9 @@ class ImplicitData:
         ptr, idx = self._net
         deg = np.diff(ptr)
         users = rng.integers(0, self.n_users, self.traindataSize)
-        users = users[deg[users] > 0]
+        # a user without positives is skipped, and so is one without a free item: no negative exists for it, and
+        # rk_bpr_sample answers valid = 0 for both
+        users = users[(deg[users] > 0) & (deg[users] < self.n_items)]
         pos = idx[ptr[users] + (rng.random(len(users)) * deg[users]).astype(np.int64)]
         neg = rng.integers(0, self.n_items, len(users))
         todo = np.arange(len(users))
@@ -294,7 +296,9 @@ class ImplicitData:
         ratio = self.config["negative_ratio"]
         pu = np.repeat(np.arange(self.n_users, dtype=np.int64), deg)
         pi = idx.astype(np.int64)
-        nu = np.repeat(np.arange(self.n_users, dtype=np.int64), deg * ratio)
+        # a user who has interacted with every item has no negative to draw (the reference cannot draw one either):
+        # it contributes its positives only
+        nu = np.repeat(np.arange(self.n_users, dtype=np.int64), np.where(deg < self.n_items, deg * ratio, 0))
         # k-th free item of user u: draw a rank in the complement and skip over the sorted positives
         free = (self.n_items - deg)[nu]
         r = (rng.random(len(nu)) * free).astype(np.int64)
@@ -320,6 +324,10 @@ class ImplicitData:
         if not hasattr(self, key):
             ptr, idx = self._net if pairwise else self.train_csr_sorted()
             setattr(self, key, (torch.as_tensor(ptr, dtype=torch.int32).to(dev), torch.as_tensor(idx, dtype=torch.int32).to(dev)))
+            # users without a free item (pointwise): rk_pointwise_sample writes (u, 0, label 0) for them, dropped below
+            if not pairwise:
+                full = np.diff(np.asarray(ptr)) >= self.n_items
+                self._dev_full = torch.as_tensor(full).to(dev) if full.any() else None
         ptr, idx = getattr(self, key)
         gen = torch.Generator(device=dev)
         gen.manual_seed(seed & 0x7FFFFFFF)
@@ -340,6 +348,9 @@ class ImplicitData:
             _lib.check(_lib.lib().rk_pointwise_sample(self.n_users, self.n_items, _lib.ptr(ptr), _lib.ptr(idx), E, ratio, seed,
                                                       _lib.ptr(cols[0]), _lib.ptr(cols[1]), _lib.ptr(cols[2]), _lib.stream_ptr()),
                        "rk_pointwise_sample")
+            if self._dev_full is not None:
+                keep = ~(self._dev_full[cols[0]] & (cols[2] == 0))
+                cols = [c[keep] for c in cols]
             names, bs = ("users", "items", "labels"), self.config["pointwise_batch_size"]
         perm = torch.randperm(cols[0].numel(), device=dev, generator=gen)
         out = {k: c[perm].contiguous() for k, c in zip(names, cols)}
