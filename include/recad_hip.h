@@ -610,6 +610,45 @@ int rk_pca_update(int64_t n, const float *V, int32_t p, const double *M, int32_t
  * PCASelectUsers.py:80 (one 64-bit radix key per user).  Synchronous; RK_EINVAL when a distance is not finite. */
 int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *order, void *stream);
 
+/* KnnSelectUsers: DegSim, a profile's mean cosine similarity to its k nearest neighbours (Chirita et al. 2005; Burke /
+ * Mobasher et al. 2006), exact and repeatable.  It has no counterpart in the reference; the definition is this:
+ *   q_e = (int) val_e, every value an integer in 1..127; column ids strictly ascending inside a row, in [0, n_items);
+ *   d_uv = sum_i q_ui q_vi in integers; n_u = d_uu < 2^31 (so every d_uv fits int32);
+ *   r_u = (float)(1.0 / sqrt((double) n_u)) (IEEE fp64 sqrt and divide, one rounding), 0 for an empty row;
+ *   w_uv = ((float) d_uv * r_u) * r_v: round-to-nearest conversion, two fp32 multiplies in that order, no contraction;
+ *   candidates of u: every v != u (w = 0 without overlap); k_eff = min(k, U - 1);
+ *   topw[u, 0..k) = the k_eff largest w_uv in descending order, padded with 0.0f (values only, never ids);
+ *   degsim[u] = (float)(s / k_eff), s the fp64 sum of topw[u, 0..k_eff) in that order; 0 when k_eff == 0 or the row is empty.
+ * recad_amd/defense/knn_select_users.py drives these entries.  All pointers are device pointers. */
+#define RK_KNN_MAX_K 128
+/* Users whose int32 accumulators one workgroup holds at once: 4 * band bytes plus the selection scratch (top list, one
+ * 2048-bin digit histogram, hand-over words: 8768 bytes) within the 160 KiB of a CU's LDS. */
+#define RK_KNN_MAX_BAND 38720
+/* status[0] of rk_knn_norms */
+#define RK_KNN_BAD_VALUE 1    /* a value that is not an integer in 1..127 (NaN, 0, 128, 2.5, -1 ...) */
+#define RK_KNN_BAD_COLUMN 2   /* column ids of a row not strictly ascending, or outside [0, n_items) */
+#define RK_KNN_BAD_NORM 3     /* n_u >= 2^31 */
+#define RK_KNN_BAD_ROWPTR 4   /* rowptr[u] negative or above rowptr[u + 1]: the row is not read */
+/* Validates the rules above and writes rnorm[u] = r_u.  Synchronous: reads status (device, int32[2]) back.  Without a
+ * violation status = {0, -1}.  With one: RK_EINVAL, status = {rule, row} of the lowest offending row (of several rules broken
+ * in that row the lowest-numbered one) and rnorm is UNTOUCHED: the values are formed in a temporary and copied on success. */
+int rk_knn_norms(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val, float *rnorm /*[U]*/,
+                 int32_t *status /*int32[2]*/, void *stream);
+/* topw and degsim of every user, from a CSR that passed rk_knn_norms, its rnorm, and its transpose colptr / crow / cval
+ * (rk_pca_transpose: users ascending inside a column -- each column is binary-searched for a band's segment).  One
+ * workgroup per user; the dots of `band` candidate users at a time are accumulated with integer LDS atomics (exact in any
+ * arrival order), turned into w and folded into a running top-k of values by a radix select on their bit patterns.
+ * band: 0 = automatic (the users in equal bands of at most 8192), else a multiple of 64 in 64..RK_KNN_MAX_BAND.
+ * 1 <= k <= RK_KNN_MAX_K.  order ([U] or NULL): a permutation of the users, workgroup b takes user order[b] (longest work
+ * first); results do not depend on it; an entry outside [0, U) is skipped.  topw ([U * k]) may be NULL.  Asynchronous.
+ * RK_EINVAL with nothing launched and nothing written: k or band out of range, a missing pointer. */
+int rk_knn_degsim(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
+                  const int32_t *colptr, const int32_t *crow, const float *cval, const float *rnorm, int32_t k, int32_t band,
+                  const int32_t *order /*[U] or NULL*/, float *topw /*[U*k] or NULL*/, float *degsim /*[U]*/, void *stream);
+/* order_out[0..m) = the ids of the m smallest scores, or of the m largest when largest != 0; ties to the lower id (-0.0
+ * and 0.0 are equal).  The radix sort of rk_pca_select.  Synchronous; RK_EINVAL on a non-finite score or m outside 0..n. */
+int rk_knn_select(int32_t n, const float *score, int32_t m, int32_t largest, int32_t *order_out, void *stream);
+
 /* ---------------------------------------------------------------- attacker --------- */
 /* AUSH (recad/model/attacker/aush.py, registry recad/default.py:159-168) without the dense U x I train_mat
  * (explicit.py:102,134-143) and the dense B x I batches (explicit.py:178-199, aush.py:92-134): each attack row is the sparse

@@ -118,6 +118,10 @@ struct RkScratch {
     }
 };
 
+// order[0..m) = the ids of the m smallest scores (the m largest when `largest`), ties to the lower id; synchronous; RK_EINVAL on a
+// non-finite score or m outside 0..n (pca.hip; the body of rk_pca_select and rk_knn_select, `who` / `noun` word its messages)
+int rk_select_ids(const char *who, const char *noun, int32_t n, const float *score, int32_t m, int32_t largest, int32_t *order, void *stream);
+
 // Stream-ordered zero fill by a kernel.  Used instead of hipMemsetAsync where the NEXT launch on the stream
 // accumulates into the buffer with atomics: as the trailing node of a replayed hipGraph a memset node was
 // observed to overlap the next replay's first kernel on this stack (lightgcn.hip, launch_backward), so

@@ -322,7 +322,9 @@ RK_EXPORT int rk_pca_update(int64_t n, const float *V, int32_t p, const double *
 // ---- selection: the m smallest (dist, id) pairs in Python's stable ascending sort order (PCASelectUsers.py:80-90).
 // Key = order-preserving encoding of the fp32 distance in the high 32 bits, the user id in the low 32: one radix sort
 // gives ties to the lower id, exactly like sorted(..., key=dist).  Non-finite distances are counted and refused.
-__global__ void pca_select_keys_kernel(int n, const float *__restrict__ dist, unsigned long long *__restrict__ keys, int *__restrict__ bad)
+// `largest`: the encoding is complemented, so the same ascending sort lists the largest first, ties still to the lower id.
+__global__ void pca_select_keys_kernel(int n, const float *__restrict__ dist, int largest, unsigned long long *__restrict__ keys,
+                                       int *__restrict__ bad)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -331,6 +333,7 @@ __global__ void pca_select_keys_kernel(int n, const float *__restrict__ dist, un
     if (d == 0.0f) d = 0.0f;    // -0 and +0 compare equal in Python: one key
     unsigned u = __float_as_uint(d);
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    if (largest) u = ~u;
     keys[i] = ((unsigned long long)u << 32) | (unsigned)i;
 }
 
@@ -340,9 +343,10 @@ __global__ void pca_select_out_kernel(int m, const unsigned long long *__restric
     if (i < m) ids[i] = (int)(sorted[i] & 0xffffffffULL);
 }
 
-RK_EXPORT int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *order, void *stream)
+// shared by rk_pca_select and rk_knn_select (declared in common.h)
+int rk_select_ids(const char *who, const char *noun, int32_t n, const float *dist, int32_t m, int32_t largest, int32_t *order, void *stream)
 {
-    if (n <= 0 || m < 0 || m > n || !dist || !order) RK_FAIL(RK_EINVAL, "rk_pca_select: bad arguments");
+    if (n <= 0 || m < 0 || m > n || !dist || !order) RK_FAIL(RK_EINVAL, "%s: bad arguments", who);
     hipStream_t s = (hipStream_t)stream;
     RkScratch scratch(s);
     unsigned long long *keys = nullptr, *sorted = nullptr;
@@ -355,7 +359,7 @@ RK_EXPORT int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *or
     RK_HIP(scratch.get(&bad, 1));
     RK_HIP(scratch.bytes(&tmp, tmp_bytes));
     RK_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
-    hipLaunchKernelGGL(pca_select_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, dist, keys, bad);
+    hipLaunchKernelGGL(pca_select_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, dist, largest, keys, bad);
     RK_CHECK_LAUNCH();
     RK_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, tmp_bytes, keys, sorted, n, 0, 64, s));
     if (m > 0) {
@@ -365,6 +369,11 @@ RK_EXPORT int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *or
     int h_bad = 0;
     RK_HIP(hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, s));
     RK_HIP(hipStreamSynchronize(s));
-    if (h_bad) RK_FAIL(RK_EINVAL, "rk_pca_select: %d non-finite distances", h_bad);
+    if (h_bad) RK_FAIL(RK_EINVAL, "%s: %d non-finite %s", who, h_bad, noun);
     return RK_OK;
+}
+
+RK_EXPORT int rk_pca_select(int32_t n, const float *dist, int32_t m, int32_t *order, void *stream)
+{
+    return rk_select_ids("rk_pca_select", "distances", n, dist, m, 0, order, stream);
 }

@@ -57,7 +57,9 @@ MODEL = {
                 "budget": 6, "hops": "elementwise", "seed": None},
     },
     # recad/default.py:223-228; block / tol / max_iter / seed are this build's solver knobs (block None = 8, or 16 when kVals > 5)
-    "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED}},
+    "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED},
+                 # build-specific (no reference counterpart): DegSim neighbour detection, defense/knn_select_users.py
+                 "KnnSelectUsers": {"k": 25, "attack_num": 50, "select": "low", "band": None, "schedule": "work"}},
 }
 for _scope in MODEL.values():
     for _cfg in _scope.values():

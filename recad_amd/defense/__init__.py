@@ -1,3 +1,4 @@
+from .knn_select_users import KnnSelectUsers
 from .pca_select_users import PCASelectUsers
 
-__all__ = ["PCASelectUsers"]
+__all__ = ["KnnSelectUsers", "PCASelectUsers"]

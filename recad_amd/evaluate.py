@@ -423,3 +423,19 @@ def hr_rows(user_ids, res, topks):
         hits = [(res["target_rank"][:, t] < k).astype(np.float64) for k in topks]
         rows.append(np.stack([np.asarray(user_ids, dtype=np.float64), res["target_score"][:, t].astype(np.float64)] + hits, 1))
     return np.concatenate(rows, 0) if rows else np.zeros((0, 2 + len(topks)))
+
+
+def detection_quality(flagged, n_real_users, n_total_users):
+    """How many of the users a defender flagged were injected: the fake users are the ids n_real_users .. n_total_users - 1
+    (inject_data appends them).  Plain host arithmetic over the DISTINCT flagged ids; an id outside [0, n_total_users) is
+    ignored (it names nobody, so it is neither a hit nor a false alarm).  precision = 0 when nothing is flagged, recall = 0
+    when nothing is fake, f1 = 0 when both are 0."""
+    n_real, n_total = int(n_real_users), int(n_total_users)
+    if not 0 <= n_real <= n_total:
+        raise ValueError(f"detection_quality: n_real_users = {n_real} outside 0..n_total_users = {n_total}")
+    ids = {int(u) for u in flagged if 0 <= int(u) < n_total}
+    tp, n_fake = sum(1 for u in ids if u >= n_real), n_total - n_real
+    precision = tp / len(ids) if ids else 0.0
+    recall = tp / n_fake if n_fake else 0.0
+    f1 = 2.0 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+    return {"precision": precision, "recall": recall, "f1": f1, "n_flagged": len(ids), "n_fake": n_fake, "true_positives": tp}

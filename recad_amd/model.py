@@ -1,12 +1,12 @@
 """model.from_config("victim" | "attacker" | "defender", name, **kw): the reference's factory (recad/model/__init__.py:3-21)
-for the victims, attackers and defender this build implements."""
+for the victims, attackers and defenders this build implements."""
 from . import attack, defense, victim
 
 factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": victim.NCF},
              "attacker": {"aia": attack.AIA, "aush": attack.Aush, "aushplus": attack.AushPlus, "random": attack.RandomAttacker,
                           "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack,
                           "uba": attack.UBA},
-             "defender": {"PCASelectUsers": defense.PCASelectUsers}}
+             "defender": {"PCASelectUsers": defense.PCASelectUsers, "KnnSelectUsers": defense.KnnSelectUsers}}
 
 
 def from_config(scope, name, **kwargs):

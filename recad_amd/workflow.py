@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from .default import WORKFLOW
-from .evaluate import eligible_users, eligible_users_device, full_catalog_topk, heldout_quality, hit_counts, hr_rows, pred_shift
+from .evaluate import detection_quality, eligible_users, eligible_users_device, full_catalog_topk, heldout_quality, hit_counts, hr_rows, pred_shift
 from .utils import NullProgress, get_logger
 
 
@@ -278,6 +278,8 @@ class Defense(Normal):
             flagged = list(self.defender.defense_step(dataset=fake_dataset))
         else:
             flagged = list(self.defender.defense_step())
+        # how many of the flagged users were injected (any defender): an attribute, the returned dict keeps its keys
+        self.detection = detection_quality(flagged, self.victim_data.n_users, fake_dataset.n_users)
         cleaned = self.victim_data.delete_data("explicit", flagged, fake_array, filter_num=self.c["filter_num"])
         self.random_seed_set()
         defended_victim = self.victim.reset().I(dataset=cleaned).to(dev)
