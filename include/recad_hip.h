@@ -649,6 +649,60 @@ int rk_knn_degsim(int32_t n_users, int32_t n_items, const int32_t *rowptr, const
  * and 0.0 are equal).  The radix sort of rk_pca_select.  Synchronous; RK_EINVAL on a non-finite score or m outside 0..n. */
 int rk_knn_select(int32_t n, const float *score, int32_t m, int32_t largest, int32_t *order_out, void *stream);
 
+/* ItemKNN victim: item-neighbourhood collaborative filtering (Sarwar et al. 2001; Deshpande and Karypis 2004), exact and
+ * repeatable.  It has no counterpart in the reference; the definition is this:
+ *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending);
+ *   q = (int) val; d_ij = sum_u q_ui q_uj in integers; n_i = d_ii < 2^31 (so every d_ij fits int32);
+ *   r_i = (float)(1.0 / sqrt((double) n_i)), 0 for an item nobody rated (rk_knn_norms applied to the transpose);
+ *   w_ij = ((float) d_ij * r_i) * r_j: one conversion, two fp32 multiplies in that order, no contraction (the operations and
+ *   order of the KnnSelectUsers definition, applied to columns);
+ *   candidates of item i: every j != i with d_ij > 0, ordered by (w_ij descending, j ascending); k_eff = min(k, I - 1);
+ *   the first k_eff candidates fill slots t = 0, 1, ... of item i; unused slots hold id -1 and w = +0.0f;
+ *   layout, slot-major: nbr_id[t * n_items + i] (int32), nbr_w[t * n_items + i] (float32), t in [0, k): lanes of the scoring
+ *   kernel own consecutive items and read slot t of all of them as one coalesced line;
+ *   score(u, i) = s_k, s_0 = +0.0f, s_{t+1} = s_t + fl(w_t * (float) q_{u, id_t}): fp32, no contraction, t ascending; a slot
+ *   with id -1 or an item u has not rated contributes nothing (the same bits as adding +0.0f: every partial sum is >= 0).
+ *   The un-normalised sum of Deshpande and Karypis (2004): no denominator, no shrinkage.  Items u has rated are scored like
+ *   any other; excluding them is rk_topk_rows' job.
+ * w carries at most five roundings, each term one more and the sum k - 1 more: every score lies within
+ * (k + 6) * 2^-24 * sum_t w_t q_t of the float64 evaluation of the same neighbour list.
+ * recad_amd/victim/itemknn.py drives these entries.  All pointers are device pointers. */
+/* Candidate items whose int32 accumulators one neighbour workgroup holds at once: 4 * band bytes plus the selection scratch
+ * (512 64-bit keys: the running list, 256 pending candidates, padding; hand-over words: 4160 bytes) within the 160 KiB of a
+ * CU's LDS. */
+#define RK_ITEMKNN_MAX_BAND 39872
+/* The largest catalogue rk_itemknn_scores takes: one user's row as bytes, one per item, within a CU's LDS (160 KiB less the 64
+ * bytes every kernel here leaves free; the kernel needs no other LDS). */
+#define RK_ITEMKNN_MAX_ITEMS 163776
+#define RK_ITEMKNN_MAX_USER_BLOCK 16
+/* The neighbour tables of every item, from a CSR that passed rk_knn_norms, its transpose colptr / crow / cval
+ * (rk_pca_transpose) and rnorm_item = the rnorm rk_knn_norms gives for the transpose.  One workgroup per item; the dots of
+ * `band` candidate items at a time are accumulated with integer LDS atomics (exact in any arrival order); the candidates become
+ * 64-bit keys (bits of w) << 32 | (0xFFFFFFFF - j), all distinct, of which the k_eff largest are kept and sorted.
+ * band: 0 = automatic (the items in equal bands of at most 8192), else a multiple of 64 in 64..RK_ITEMKNN_MAX_BAND.
+ * 1 <= k <= RK_KNN_MAX_K.  order ([I] or NULL): a permutation of the items, workgroup b takes item order[b]; results do not
+ * depend on it; an entry outside [0, I) is skipped.  Every slot of both tables is written.  Asynchronous.
+ * RK_EINVAL with nothing launched and nothing written: k or band out of range, a missing pointer. */
+int rk_itemknn_neighbors(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
+                         const int32_t *colptr, const int32_t *crow, const float *cval, const float *rnorm_item, int32_t k,
+                         int32_t band, const int32_t *order /*[I] or NULL*/, int32_t *nbr_id /*[k*I]*/, float *nbr_w /*[k*I]*/,
+                         void *stream);
+/* out[b * n_items + i] = score(user_ids[b], i) for b in [0, nb), every i: every element of out is written.  A workgroup
+ * stages user_block users' rows in LDS as dense byte rows (q <= 127) and walks the items, so each table entry is read once per
+ * user block and feeds user_block accumulators, each summed in slot order.  user_block: 0 = automatic (what fits, at most
+ * RK_ITEMKNN_MAX_USER_BLOCK), else 1..RK_ITEMKNN_MAX_USER_BLOCK, refused when that many rows of n_items bytes (padded to 16) do
+ * not fit.  user_ids ([nb], int32, in [0, U); repeats allowed) are not checked.  Asynchronous; nb = 0 launches nothing.
+ * RK_EINVAL with nothing launched and nothing written: k or user_block out of range, n_items > RK_ITEMKNN_MAX_ITEMS, a
+ * missing pointer. */
+int rk_itemknn_scores(int32_t n_items, int32_t k, const int32_t *nbr_id, const float *nbr_w, const int32_t *rowptr,
+                      const int32_t *col, const float *val, int32_t nb, const int32_t *user_ids, int32_t user_block,
+                      float *out /*[nb * n_items]*/, void *stream);
+/* out[p] = score(users[p], items[p]), p in [0, n): the same sum in the same order, so the same bits as the matrix entry.  A
+ * pair whose user or item id is out of range scores 0.0 and reads nothing.  Asynchronous; n = 0 launches nothing. */
+int rk_itemknn_pair_scores(int32_t n_items, int32_t n_users, int32_t k, const int32_t *nbr_id, const float *nbr_w,
+                           const int32_t *rowptr, const int32_t *col, const float *val, const int64_t *users /*[n]*/,
+                           const int64_t *items /*[n]*/, int64_t n, float *out /*[n]*/, void *stream);
+
 /* ---------------------------------------------------------------- attacker --------- */
 /* AUSH (recad/model/attacker/aush.py, registry recad/default.py:159-168) without the dense U x I train_mat
  * (explicit.py:102,134-143) and the dense B x I batches (explicit.py:178-199, aush.py:92-134): each attack row is the sparse

@@ -22,6 +22,7 @@ RK_RANK_MAX_NK = 8   # cut-offs per rk_rank_metrics call
 RK_KNN_MAX_K, RK_KNN_MAX_BAND = 128, 38720
 RK_KNN_RULES = {1: "a value that is not an integer in 1..127", 2: "column ids not strictly ascending inside [0, n_items)",
                 3: "a squared norm of 2^31 or more", 4: "row pointers that decrease or are negative"}
+RK_ITEMKNN_MAX_BAND, RK_ITEMKNN_MAX_ITEMS, RK_ITEMKNN_MAX_USER_BLOCK = 39872, 163776, 16
 
 
 class HipLibraryMissing(RuntimeError):
@@ -251,6 +252,9 @@ _SIGNATURES = {
     "rk_knn_norms": [_I32, _I32, _P, _P, _P, _P, _P, _P],
     "rk_knn_degsim": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
     "rk_knn_select": [_I32, _P, _I32, _I32, _P, _P],
+    "rk_itemknn_neighbors": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
+    "rk_itemknn_scores": [_I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P],
+    "rk_itemknn_pair_scores": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P],
     "rk_aush_workspace_bytes": [_I32, _I32, _I32, C.POINTER(_I64)],
     "rk_aush_eligible": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, C.POINTER(_I32), _P],
     "rk_aush_permute": [_I32, _P, C.c_uint64, C.c_uint64, _P, _P],

@@ -23,6 +23,8 @@ MODEL = {
             "factor_num": 32, "num_layers": 5, "dropout": 0, "model": "NeuMF-end", "GMF_model": None, "MLP_model": None,
             "optim": "adam", "lr": 1e-3,
         },
+        # build-specific (no reference counterpart): item-neighbourhood CF, victim/itemknn.py; band / user_block None = automatic
+        "itemknn": {"k": 50, "band": None, "user_block": None},
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},

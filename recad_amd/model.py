@@ -2,7 +2,8 @@
 for the victims, attackers and defenders this build implements."""
 from . import attack, defense, victim
 
-factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": victim.NCF},
+factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": victim.NCF,
+                        "itemknn": victim.ItemKNN},
              "attacker": {"aia": attack.AIA, "aush": attack.Aush, "aushplus": attack.AushPlus, "random": attack.RandomAttacker,
                           "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack,
                           "uba": attack.UBA},
