@@ -585,6 +585,14 @@ RK_EXPORT int rk_ncf_train_epoch(const rk_ncf_desc *desc, const int64_t *users, 
     for (int t = 0; t < T; ++t)
         if (!d.grad[t] || !d.m[t] || !d.v[t]) RK_FAIL(RK_EINVAL, "ncf: grad/moment pointer %d missing", t);
     if (!d.wgrad_part) RK_FAIL(RK_EINVAL, "ncf: desc.wgrad_part missing");
+    // gemm_fwd_blocked refuses a scratch it cannot work in, but only once the step is under way (gradients and loss partials
+    // zeroed, the gather launched): refuse here, while nothing has been written
+    if (d.mode != RK_NCF_GMF)
+        for (int l = 0; l < L; ++l) {
+            const long long out = in_of(d, l) / 2, need = (long long)kFwdBlocks * 64 * out;
+            if (fwd_blocked(in_of(d, l)) && (!d.gemm_scratch || d.gemm_scratch_floats < need || out % 4))
+                RK_FAIL(RK_EINVAL, "ncf: layer %d's blocked forward needs desc.gemm_scratch of >= %lld floats", l, need);
+        }
     hipStream_t s = (hipStream_t)stream;
     // tensor order: ug, ig, um, im, W0.., b0.., pw, pb
     float *P[RK_NCF_MAX_TENSORS];
