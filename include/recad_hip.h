@@ -703,6 +703,70 @@ int rk_itemknn_pair_scores(int32_t n_items, int32_t n_users, int32_t k, const in
                            const int32_t *rowptr, const int32_t *col, const float *val, const int64_t *users /*[n]*/,
                            const int64_t *items /*[n]*/, int64_t n, float *out /*[n]*/, void *stream);
 
+/* EASE victim: the linear item-item autoencoder with a closed-form fit (Steck 2019, "Embarrassingly Shallow Autoencoders for
+ * Sparse Data"), repeatable to the bit.  It has no counterpart in the reference; the definition is this:
+ *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending);
+ *   q = (int) val; d_ij = sum_u q_ui q_uj in integers; every d_ii < 2^24, so every d_ij (<= sqrt(d_ii d_jj)) is exactly
+ *   representable in fp32; a larger d_ii is refused, reported as {RK_EASE_BAD_GRAM, item} the way rk_knn_norms reports;
+ *   A_ij = (float) d_ij for i != j, A_ii = (float) d_ii + lambda: one fp32 add, lambda a finite fp32 > 0; A is row-major
+ *   [I * I] with 64-bit offsets, symmetric positive definite with smallest eigenvalue >= lambda;
+ *   P = A^-1, computed in place on the device in fp32.  This is the only step that is not pinned to the bit: it is pinned by
+ *   an error budget.  With A64 the float64 copy of A, P* = inv(A64) and kappa the ratio of A64's extreme eigenvalues,
+ *   max|P - P*| <= I * 2^-24 * kappa * max|P*| (the forward bound of a backward-stable inverse with constant 1), and the tests
+ *   hold it to 4 x the error of a plain fp32 numpy walk of the same algorithm plus 2^-23 max|P*|
+ *   (tests/_ease_restate.py).  Two runs on the same input give the same bits: nothing in the inverse adds floats atomically;
+ *   B_ij = -(float)((double) P_ij / (double) P_jj) for i != j, B_jj = +0.0f, row-major [I * I]: the divisor is the diagonal
+ *   of the COLUMN (dividing by P_ii gives B transposed);
+ *   score(u, j) = s_n, s_0 = +0.0f, s_{e+1} = s_e + fl((float) q_{u, i_e} * B[i_e, j]) over u's stored entries in column
+ *   order: fp32, no contraction.  Items u has rated are scored like any other; excluding them is rk_topk_rows' job.  A user
+ *   with no entries scores +0.0f everywhere.
+ * recad_amd/victim/ease.py drives these entries.  All pointers are device pointers. */
+/* The largest catalogue: B is I x I fp32, 4 * 65536^2 bytes = 16 GiB at the limit (the yelp-shaped 34 474 items take 4.75 GB).
+ * The inverse runs in B's own storage and its workspace is I * block floats (16 MiB at the limit), so a fit holds one I x I
+ * matrix; a workflow that keeps the clean and the poisoned victim holds two, 32 GiB of an MI355X's 288 GB, which leaves the
+ * score chunks (chunk * I floats) and the dataset.  The tile grids index 65536 / 64 = 1024 tiles a side. */
+#define RK_EASE_MAX_ITEMS 65536
+/* The widths of a block step of rk_ease_invert.  A pivot block is inverted inside one workgroup's LDS (64 x 65 floats), and a
+ * 64 x 64 tile of the panels and of the trailing update takes its whole k range from two such arrays (33 KiB). */
+#define RK_EASE_BLOCK_SMALL 32
+#define RK_EASE_BLOCK_LARGE 64
+/* status[0] of rk_ease_gram and rk_ease_invert (the numbering continues RK_KNN_BAD_*) */
+#define RK_EASE_BAD_GRAM 5    /* d_ii >= 2^24: status[1] is the lowest such item */
+#define RK_EASE_NOT_SPD 6     /* a pivot that is not a finite number > 0: status[1] is its index */
+/* A ([I * I]) from the CSR and its transpose colptr / crow / cval (rk_pca_transpose), lambda added to the diagonal.  One
+ * workgroup per row of A; the dots of 8192 columns at a time are accumulated with integer LDS atomics (exact in any arrival
+ * order) and converted once.  Every element of A is written.  Synchronous: the d_ii rule is validated first and status
+ * (device, int32[2]) read back.  Without a violation status = {0, -1}.  With one: RK_EINVAL, status = {RK_EASE_BAD_GRAM, item}
+ * and A is UNTOUCHED.  RK_EINVAL with nothing launched and nothing written: I < 1 or above RK_EASE_MAX_ITEMS, lambda not
+ * finite or <= 0, a missing pointer. */
+int rk_ease_gram(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
+                 const int32_t *colptr, const int32_t *crow, const float *cval, float lambda, float *A /*[I*I]*/,
+                 int32_t *status /*int32[2]*/, void *stream);
+/* A <- A^-1 in place: a blocked Gauss-Jordan sweep without pivoting (A symmetric positive definite).  Per block K of `block`
+ * indices: D = inv(A_KK) inside one workgroup's LDS; A_Kj <- D A_Kj and A_iK <- -A_iK D for i, j outside K, with the old A_iK
+ * kept in work; A_ij <- A_ij - (old A_iK) A_Kj, the product summed in k order on the fp32 MFMA and subtracted once.  block: 0 = automatic
+ * (RK_EASE_BLOCK_SMALL up to 32 items, else RK_EASE_BLOCK_LARGE), or one of the two.  work: at least I * block floats (block as
+ * resolved), never a second I x I.  Synchronous: status (device, int32[2]) is read back, {0, -1} on success.  A pivot that
+ * is not a finite number > 0 stops the sweep (every later kernel returns at once; all device loops are bounded by I):
+ * RK_EINVAL, status = {RK_EASE_NOT_SPD, pivot index}, and nothing is claimed about A.  RK_EINVAL with nothing launched and
+ * nothing written: I < 1 or above RK_EASE_MAX_ITEMS, an unsupported block, too little workspace, a missing pointer. */
+int rk_ease_invert(int32_t n_items, float *A /*[I*I]*/, float *work, int64_t work_floats, int32_t block,
+                   int32_t *status /*int32[2]*/, void *stream);
+/* B from P as defined; B may be P (the diagonal is read out first).  Every element of B is written.  Asynchronous.
+ * RK_EINVAL with nothing launched: I out of range, a missing pointer. */
+int rk_ease_weights(int32_t n_items, const float *P /*[I*I]*/, float *B /*[I*I]*/, void *stream);
+/* out[b * n_items + j] = score(user_ids[b], j) for b in [0, nb), every j: every element of out is written.  One workgroup per
+ * user and 256 consecutive items, one item per lane, so each row of B is read as coalesced lines.  user_ids ([nb], int32, in
+ * [0, U); repeats and users with empty rows allowed) are not checked.  Asynchronous; nb = 0 launches nothing.
+ * RK_EINVAL with nothing launched and nothing written: I out of range, nb < 0, a missing pointer. */
+int rk_ease_scores(int32_t n_items, const float *B, const int32_t *rowptr, const int32_t *col, const float *val, int32_t nb,
+                   const int32_t *user_ids, float *out /*[nb * n_items]*/, void *stream);
+/* out[p] = score(users[p], items[p]), p in [0, n): the same sum in the same order, so the same bits as the matrix entry.  A
+ * pair whose user or item id is out of range scores 0.0 and reads nothing.  Asynchronous; n = 0 launches nothing. */
+int rk_ease_pair_scores(int32_t n_items, int32_t n_users, const float *B, const int32_t *rowptr, const int32_t *col,
+                        const float *val, const int64_t *users /*[n]*/, const int64_t *items /*[n]*/, int64_t n,
+                        float *out /*[n]*/, void *stream);
+
 /* ---------------------------------------------------------------- attacker --------- */
 /* AUSH (recad/model/attacker/aush.py, registry recad/default.py:159-168) without the dense U x I train_mat
  * (explicit.py:102,134-143) and the dense B x I batches (explicit.py:178-199, aush.py:92-134): each attack row is the sparse

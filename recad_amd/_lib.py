@@ -23,6 +23,8 @@ RK_KNN_MAX_K, RK_KNN_MAX_BAND = 128, 38720
 RK_KNN_RULES = {1: "a value that is not an integer in 1..127", 2: "column ids not strictly ascending inside [0, n_items)",
                 3: "a squared norm of 2^31 or more", 4: "row pointers that decrease or are negative"}
 RK_ITEMKNN_MAX_BAND, RK_ITEMKNN_MAX_ITEMS, RK_ITEMKNN_MAX_USER_BLOCK = 39872, 163776, 16
+RK_EASE_MAX_ITEMS, RK_EASE_BLOCK_SMALL, RK_EASE_BLOCK_LARGE = 65536, 32, 64
+RK_EASE_BAD_GRAM, RK_EASE_NOT_SPD = 5, 6
 
 
 class HipLibraryMissing(RuntimeError):
@@ -255,6 +257,11 @@ _SIGNATURES = {
     "rk_itemknn_neighbors": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
     "rk_itemknn_scores": [_I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P],
     "rk_itemknn_pair_scores": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P],
+    "rk_ease_gram": [_I32, _I32, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P],
+    "rk_ease_invert": [_I32, _P, _P, _I64, _I32, _P, _P],
+    "rk_ease_weights": [_I32, _P, _P, _P],
+    "rk_ease_scores": [_I32, _P, _P, _P, _P, _I32, _P, _P, _P],
+    "rk_ease_pair_scores": [_I32, _I32, _P, _P, _P, _P, _P, _P, _I64, _P, _P],
     "rk_aush_workspace_bytes": [_I32, _I32, _I32, C.POINTER(_I64)],
     "rk_aush_eligible": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, C.POINTER(_I32), _P],
     "rk_aush_permute": [_I32, _P, C.c_uint64, C.c_uint64, _P, _P],

@@ -25,6 +25,9 @@ MODEL = {
         },
         # build-specific (no reference counterpart): item-neighbourhood CF, victim/itemknn.py; band / user_block None = automatic
         "itemknn": {"k": 50, "band": None, "user_block": None},
+        # build-specific (no reference counterpart): the closed-form item-item autoencoder (Steck 2019), victim/ease.py;
+        # block None = automatic
+        "ease": {"reg_lambda": 500.0, "block": None},
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},

@@ -1,7 +1,8 @@
 from .base import BaseVictim
+from .ease import EASE
 from .itemknn import ItemKNN
 from .lightgcn import LightGCN
 from .mf import MF
 from .ncf import NCF
 
-__all__ = ["BaseVictim", "ItemKNN", "LightGCN", "MF", "NCF"]
+__all__ = ["BaseVictim", "EASE", "ItemKNN", "LightGCN", "MF", "NCF"]
