@@ -767,6 +767,85 @@ int rk_ease_pair_scores(int32_t n_items, int32_t n_users, const float *B, const 
                         const float *val, const int64_t *users /*[n]*/, const int64_t *items /*[n]*/, int64_t n,
                         float *out /*[n]*/, void *stream);
 
+/* iALS victim: weighted matrix factorisation for implicit feedback fitted by alternating least squares (Hu, Koren and
+ * Volinsky 2008, "Collaborative Filtering for Implicit Feedback Datasets").  Given the initial item table a fit is a
+ * deterministic function of the ratings.  It has no counterpart in the reference; the definition is this:
+ *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending);
+ *   q = (int) val; factor count d, 1 <= d <= RK_IALS_MAX_DIM (any integer: the kernels pad to a multiple of 16 internally);
+ *   alpha a finite fp32 >= 0, lambda a finite fp32 > 0;
+ *   confidence: w_ui = fl(alpha * (float) q_ui), c_ui = fl(1.0f + w_ui); the preference is 1 on stored entries, 0 elsewhere;
+ *   Gram matrix: G = Y^T Y + lambda I over ALL rows of the other side's table Y ([n, d] row-major), fp32, exactly symmetric
+ *   (the lower triangle is computed and mirrored), summed in an order fixed by (n, d) alone without float atomics: blocks of
+ *   RK_IALS_GRAM_ROWS rows are each one k-ordered fmaf chain from +0.0f (the fp32 MFMA), the blocks' partials are added in
+ *   block order, lambda is added to the diagonal last.  That is at most n + 1 roundings of a sum of n exact-product terms:
+ *   |G_kl - G*_kl| <= (n + 2) * 2^-24 * (sum_i |y_ik y_il| + lambda delta_kl) against float64;
+ *   the system of a row u with stored entries e = 0 .. n_u - 1 in column order:
+ *     b_u = s_n, s_0 = +0.0f, s_{e+1} = s_e + fl(c_e * y_{i_e}) per component: fp32, no contraction, bit-exact against numpy;
+ *     A_u = G + sum_e w_e y_{i_e} y_{i_e}^T, fp32: for k >= l, t_0 = +0.0f, t_{e+1} = fma(fl(w_e * y_ek), y_el, t_e) over the
+ *     entries in column order (the fp32 MFMA; the zero padding of the last chunk of RK_IALS_CHUNK entries adds exact zeros),
+ *     then (A_u)_kl = fl(G_kl + t_n), mirrored.  The roundings: one per scaled operand, one per fma, one for the add of G; with
+ *     gamma_m = m * 2^-24 / (1 - m * 2^-24), T_kl = sum_e |w_e y_ek y_el| in float64 and e_G the budget of G above,
+ *     |(A_u)_kl - A*_kl| <= e_G + gamma_{n_u + 1} T_kl + 2^-24 (|A*_kl| + e_G + gamma_{n_u + 1} T_kl), A* in float64 from the
+ *     same fp32 tables, w the fp32 value;
+ *     x_u = A_u^-1 b_u by a Cholesky factorisation A_u = L L^T (right-looking, one column at a time: l_pp = sqrt(a_pp),
+ *     l_ip = a_ip / l_pp, a_ij <- a_ij - fl(l_ip * l_jp)), forward and back substitution column by column
+ *     (z_p = b_p / l_pp, b_i <- b_i - fl(l_ip * z_p)), all in fp32 without contraction, inside the workgroup's LDS;
+ *     a row with no entries solves G x = 0 and gives +0.0f everywhere;
+ *     a pivot (the value under the square root) that is not a finite number > 0 is a refusal, {RK_IALS_NOT_SPD, lowest such
+ *     row}: device loops stay bounded by d, and nothing is claimed about that call's output;
+ *   one sweep: X <- the rows solved from Y over the CSR, then Y <- the rows solved from the new X over the transpose
+ *   (rk_pca_transpose);
+ *   objective: J = sum_{u,i} c_ui (p_ui - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2) over all U * I pairs, evaluated in float64
+ *   on the device without the dense matrix: per row x_u^T (Y^T Y) x_u + sum_e [c_e (1 - s_e)^2 - s_e^2] + lambda |x_u|^2,
+ *   s_e the double dot of the fp32 rows; the per-row doubles are summed in row order by a fixed tree, and lambda |Y|^2 =
+ *   lambda * trace(Y^T Y) is added once;
+ *   score(u, i) = x_u . y_i through rk_pair_scores / rk_score_topk, with zero biases and mean 0.0.
+ * Conditioning.  A_u >= lambda I in exact arithmetic, so a refusal arises only from non-finite tables or from a conditioning
+ * that fp32 cannot carry.  The relative error of x_u is about 0.2 * kappa_2(A_u) * 2^-24, kappa ~ 1 + (|Y^T Y| + alpha sum_e q_e
+ * |y_e|^2) / lambda: with ratings 1..5 at density 0.15 and d in {16, 32, 64}, (alpha, lambda) = (1, 0.5) stays under kappa 1.5e2
+ * (error 9e-6) and (40, 10) under 1.2e3 (2e-4), while (40, 0.5) or lambda = 0.01 at d = 64 with fewer than d rows reaches
+ * kappa 1e6, an error of 1e-1 and, once, a negative fp32 pivot.  This is inherent to fp32 ALS; iterative refinement and fp64
+ * solves are out of scope.  The hard bound the tests hold x to (tests/_ials_restate.py derives it), beta = sum_e c_e |y_e|:
+ * max|x - x*| <= 2 * 2^-24 * kappa_2(A_u) * [d^1.5 (n + n_u + 3 d + 6) max|x*| + (n_u + 1) |beta|_2 / |A_u|_2].
+ * recad_amd/victim/ials.py drives these entries.  All pointers are device pointers; no entry adds floats atomically. */
+#define RK_IALS_MAX_DIM 128
+/* Stored entries of a row staged in LDS at once, and rows of Y in one block of the Gram matrix. */
+#define RK_IALS_CHUNK 64
+#define RK_IALS_GRAM_ROWS 256
+/* status[0] of rk_ials_half_sweep (the numbering continues RK_EASE_*) */
+#define RK_IALS_NOT_SPD 7     /* a pivot that is not a finite number > 0: status[1] is the lowest such row */
+/* G ([d * d]) = Y^T Y + lambda I as defined.  work: at least ceil(n / RK_IALS_GRAM_ROWS) * dp * dp floats, dp = d rounded up
+ * to a multiple of 16 (one partial per block of rows).  Every element of G is written.  Asynchronous.
+ * RK_EINVAL with nothing launched and nothing written: n < 1, d outside 1..RK_IALS_MAX_DIM, lambda not finite or <= 0, too
+ * little workspace, a missing pointer. */
+int rk_ials_gram(int32_t n, int32_t d, const float *Y /*[n*d]*/, float lambda, float *G /*[d*d]*/, float *work, int64_t work_floats,
+                 void *stream);
+/* GY ([d * d], double) = Y^T Y without lambda, in float64: blocks of max(32, ceil(n / 1024)) rows summed in row order, the
+ * blocks' partials in block order, mirrored.  The objective's Gram matrix.  Asynchronous (its scratch is stream-ordered). */
+int rk_ials_gram64(int32_t n, int32_t d, const float *Y /*[n*d]*/, double *GY /*[d*d]*/, void *stream);
+/* A_out[b] ([d * d], row-major, both triangles) and b_out[b] ([d]) = the system of row row_ids[b], b in [0, nb): the device
+ * code of rk_ials_half_sweep up to the factorisation.  row_ids (int32, in range; repeats and empty rows allowed) are not
+ * checked.  G: what rk_ials_gram wrote for Y.  Asynchronous; nb = 0 launches nothing.
+ * RK_EINVAL with nothing launched and nothing written: n_cols < 1, d or alpha out of range, nb < 0, a missing pointer. */
+int rk_ials_system(int32_t n_cols, int32_t d, const float *G, const int32_t *rowptr, const int32_t *col, const float *val,
+                   float alpha, const float *Y /*[n_cols*d]*/, int32_t nb, const int32_t *row_ids, float *A_out /*[nb*d*d]*/,
+                   float *b_out /*[nb*d]*/, void *stream);
+/* X_out[u] = x_u for every row u of the CSR: one workgroup per row.  The row's entries are staged in LDS RK_IALS_CHUNK at a
+ * time (the tail zero-padded to the MFMA's k = 4), the lower-triangle 16 x 16 tiles of sum_e w_e y y^T are accumulated on the
+ * fp32 MFMA, shared among the four waves, G is added, and A_u is factorised and solved in LDS (row stride dp + 1).  order
+ * ([n_rows] or NULL) as in rk_knn_degsim: workgroup b takes row order[b] (longest rows first); results do not depend on it; an
+ * entry outside [0, n_rows) is skipped.  Asynchronous: status (device, int32[2]) reads {0, -1} after a clean sweep and
+ * {RK_IALS_NOT_SPD, lowest refused row} otherwise (an unsigned atomic min over the refusing workgroups).
+ * RK_EINVAL with nothing launched and nothing written: n_rows or n_cols < 1, d or alpha out of range, a missing pointer. */
+int rk_ials_half_sweep(int32_t n_rows, int32_t n_cols, int32_t d, const float *G, const int32_t *rowptr, const int32_t *col,
+                       const float *val, float alpha, const float *Y /*[n_cols*d]*/, const int32_t *order /*[n_rows] or NULL*/,
+                       float *X_out /*[n_rows*d]*/, int32_t *status /*int32[2]*/, void *stream);
+/* J[0] = the objective as defined; partial[u] = row u's double.  GY: rk_ials_gram64 of Y.  Asynchronous.
+ * RK_EINVAL with nothing launched and nothing written: a size < 1, d, alpha or lambda out of range, a missing pointer. */
+int rk_ials_objective(int32_t n_rows, int32_t n_cols, int32_t d, const int32_t *rowptr, const int32_t *col, const float *val,
+                      float alpha, float lambda, const float *X /*[n_rows*d]*/, const float *Y /*[n_cols*d]*/,
+                      const double *GY /*[d*d]*/, double *partial /*[n_rows]*/, double *J /*[1]*/, void *stream);
+
 /* ---------------------------------------------------------------- attacker --------- */
 /* AUSH (recad/model/attacker/aush.py, registry recad/default.py:159-168) without the dense U x I train_mat
  * (explicit.py:102,134-143) and the dense B x I batches (explicit.py:178-199, aush.py:92-134): each attack row is the sparse

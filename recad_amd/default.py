@@ -28,6 +28,9 @@ MODEL = {
         # build-specific (no reference counterpart): the closed-form item-item autoencoder (Steck 2019), victim/ease.py;
         # block None = automatic
         "ease": {"reg_lambda": 500.0, "block": None},
+        # build-specific (no reference counterpart): implicit-feedback ALS (Hu, Koren and Volinsky 2008), victim/ials.py;
+        # seed None = the item table's seed is drawn from torch's global RNG at .I()
+        "ials": {"factor_num": 64, "alpha": 40.0, "reg_lambda": 10.0, "init_std": 0.01, "seed": None},
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},
