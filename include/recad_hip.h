@@ -846,6 +846,46 @@ int rk_ials_objective(int32_t n_rows, int32_t n_cols, int32_t d, const int32_t *
                       float alpha, float lambda, const float *X /*[n_rows*d]*/, const float *Y /*[n_cols*d]*/,
                       const double *GY /*[d*d]*/, double *partial /*[n_rows]*/, double *J /*[1]*/, void *stream);
 
+/* SLIM victim: sparse linear item-item weights (Ning and Karypis 2011, "SLIM: Sparse Linear Methods for Top-N Recommender
+ * Systems"): each item's column is an elastic-net regression on the other items with non-negative weights and a zero diagonal,
+ * fitted by cyclic coordinate descent and repeatable to the bit.  It has no counterpart in the reference; the definition is this:
+ *   input: the U x I rating CSR under the rules of rk_knn_norms and the d_ii rule of rk_ease_gram;
+ *   G = what rk_ease_gram(..., lambda = beta, ...) writes: G_ik = (float) d_ik off the diagonal, an exact integer, and
+ *   G_kk = fl((float) d_kk + beta), beta a finite fp32 > 0; row-major [I * I] with 64-bit offsets;
+ *   l1 a finite fp32 >= 0, sweeps an integer >= 1;
+ *   all arithmetic is fp32, every operation rounded on its own, no contraction (IEEE with gradual underflow);
+ *   column j: w_k = +0.0f for every k and r_i = G[i * I + j] for every i (the diagonal entry is included, but never read as a
+ *   coordinate); for s = 1 .. sweeps, for k = 0 .. I - 1 ascending except k = j, one coordinate step:
+ *     t = fl(r_k - l1); q = fl(t / G_kk), a correctly rounded division; v = fl(w_k + q); w' = v > 0 ? v : +0.0f;
+ *     delta = fl(w' - w_k); when delta == 0 nothing happens; otherwise w_k = w' and r_i = fl(r_i - fl(delta * G[k * I + i])) for
+ *     every i in [0, I), i = k and i = j included: ROW k of G is the one read;
+ *   a coordinate with w_k == +0 and r_k <= l1 always gives delta == 0 and may be passed over without dividing; a sweep that
+ *   changes no coordinate leaves the state as it is for every later sweep, so a column stops there;
+ *   W[k * I + j] = w_k, W[j * I + j] = +0.0f: W is oriented like EASE's B, and score(u, j) is rk_ease_scores /
+ *   rk_ease_pair_scores on W unchanged;
+ *   info[3 * j + 0] = the index (from 1) of the last sweep that changed a coordinate of column j, 0 when none did,
+ *   info[3 * j + 1] = the number of w_k > 0, info[3 * j + 2] = the number of steps with delta != 0;
+ *   R_out[i * I + j] = r_i after the last sweep.
+ * Each column minimises f_j(w) = 1/2 w^T G w - d_j^T w + l1 sum_k w_k over w >= 0, w_j = 0: the L2 weight is beta / 2 on |w|^2.
+ * recad_amd/victim/slim.py drives the entry.  All pointers are device pointers. */
+/* The largest catalogue.  One workgroup owns a column and keeps r and w in LDS, 8 * I bytes, beside 64 bytes in which its four
+ * waves agree on the next coordinate.  A gfx950 workgroup may take 160 KiB = 163 840 bytes, of which the library's launches
+ * leave 64 unused: (163 840 - 64 - 64) / 8 = 20 464 items.  A fit holds two I x I fp32 matrices, G (a temporary) and W:
+ * 2 * 4 * 20 464^2 bytes = 3.35 GB at the limit.  The yelp-shaped catalogue (34 474 items) is out of reach: it is refused. */
+#define RK_SLIM_MAX_ITEMS 20464
+/* status[0] of rk_slim_fit (the numbering continues RK_IALS_*) */
+#define RK_SLIM_BAD_DIAG 8    /* a G_kk that is not a finite number > 0: status[1] is the lowest such k */
+/* W ([I * I]) from G as defined; info ([3 * I]) and R_out ([I * I]) may each be NULL.  One workgroup per column: 256
+ * coordinates at a time are worked out from the current r, the lowest one whose step is not zero is applied (row k of G read
+ * as coalesced lines, the update of r spread over the workgroup), and the coordinates after it are worked out again.  Every
+ * element of W, info and R_out is written.  All device loops are bounded by I and sweeps; nothing adds floats atomically.
+ * The diagonal is validated first and status (device, int32[2]) read back, which is the call's only synchronisation: {0, -1}
+ * without a violation; with one RK_EINVAL, status = {RK_SLIM_BAD_DIAG, lowest index} and W, info and R_out are UNTOUCHED.
+ * RK_EINVAL with nothing launched and nothing written: I < 1 or above RK_SLIM_MAX_ITEMS, sweeps < 1, l1 negative or not
+ * finite, G, W or status missing. */
+int rk_slim_fit(int32_t n_items, const float *G /*[I*I]*/, float l1, int32_t sweeps, float *W /*[I*I]*/,
+                int32_t *info /*[3*I] or NULL*/, float *R_out /*[I*I] or NULL*/, int32_t *status /*int32[2]*/, void *stream);
+
 /* ---------------------------------------------------------------- attacker --------- */
 /* AUSH (recad/model/attacker/aush.py, registry recad/default.py:159-168) without the dense U x I train_mat
  * (explicit.py:102,134-143) and the dense B x I batches (explicit.py:178-199, aush.py:92-134): each attack row is the sparse

@@ -26,6 +26,7 @@ RK_ITEMKNN_MAX_BAND, RK_ITEMKNN_MAX_ITEMS, RK_ITEMKNN_MAX_USER_BLOCK = 39872, 16
 RK_EASE_MAX_ITEMS, RK_EASE_BLOCK_SMALL, RK_EASE_BLOCK_LARGE = 65536, 32, 64
 RK_EASE_BAD_GRAM, RK_EASE_NOT_SPD = 5, 6
 RK_IALS_MAX_DIM, RK_IALS_CHUNK, RK_IALS_GRAM_ROWS, RK_IALS_NOT_SPD = 128, 64, 256, 7
+RK_SLIM_MAX_ITEMS, RK_SLIM_BAD_DIAG = 20464, 8
 
 
 class HipLibraryMissing(RuntimeError):
@@ -268,6 +269,7 @@ _SIGNATURES = {
     "rk_ials_system": [_I32, _I32, _P, _P, _P, _P, _F, _P, _I32, _P, _P, _P, _P],
     "rk_ials_half_sweep": [_I32, _I32, _I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P],
     "rk_ials_objective": [_I32, _I32, _I32, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P],
+    "rk_slim_fit": [_I32, _P, _F, _I32, _P, _P, _P, _P, _P],
     "rk_aush_workspace_bytes": [_I32, _I32, _I32, C.POINTER(_I64)],
     "rk_aush_eligible": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, C.POINTER(_I32), _P],
     "rk_aush_permute": [_I32, _P, C.c_uint64, C.c_uint64, _P, _P],

@@ -31,6 +31,9 @@ MODEL = {
         # build-specific (no reference counterpart): implicit-feedback ALS (Hu, Koren and Volinsky 2008), victim/ials.py;
         # seed None = the item table's seed is drawn from torch's global RNG at .I()
         "ials": {"factor_num": 64, "alpha": 40.0, "reg_lambda": 10.0, "init_std": 0.01, "seed": None},
+        # build-specific (no reference counterpart): sparse linear item-item weights by coordinate descent (Ning and Karypis 2011),
+        # victim/slim.py; l2_reg is the constant added to the Gram matrix's diagonal
+        "slim": {"l1_reg": 1.0, "l2_reg": 5.0, "sweeps": 50},
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},

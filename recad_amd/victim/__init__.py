@@ -5,5 +5,6 @@ from .itemknn import ItemKNN
 from .lightgcn import LightGCN
 from .mf import MF
 from .ncf import NCF
+from .slim import SLIM
 
-__all__ = ["BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "NCF"]
+__all__ = ["BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "NCF", "SLIM"]
