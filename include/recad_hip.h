@@ -1149,6 +1149,29 @@ int rk_ap_g_backward(int32_t n_rows, int32_t n_items, const int32_t *rowptr, con
 int rk_ap_d_step(int32_t n_items, int32_t nA, const int32_t *rowptrA, const int32_t *colA, const float *valA, float labelA, int32_t nB,
                  const int32_t *rowptrB, const int32_t *colB, const float *valB, float labelB, const float *dparam, float *work,
                  const int32_t *tptr, const int32_t *trow, const int32_t *tsrc, float *dgrad, float *dinB, float *loss, void *stream);
+/* What the kernel tests hold the three entries to (tests/_aushplus_stages.py counts every rounding; u = 2^-24, T = 4 the allowance
+ * of tanhf / expf / logf from the HIP math API's accuracy table, doubled), each stage against float64 on the stage's own inputs as
+ * they stand in the caller's buffers.  G forward: norm (K / 2 + 2) u norm over a row of K entries, exactly 1e-12f for an empty or
+ * all-zero row; h1 (K + 4) u (sum|x w| / norm + |b1|); a: the logit's (128 + 8) u (sum|w h| + |b2|) through 2.5 tanh, plus
+ * (T + 2) u 2.5 |tanh z| + u |a|; cls and value from a: bits (boundaries, differences and the four strict comparisons in fp32,
+ * nothing contracted).  G backward: bbar, zbar, eloss from a within the sum of the roundings of tanhf(a - b_k), 1 - th^2, the sums
+ * over the classes, mode 1's expf / logf and h2 = (a - 2.5) / 2.5; dpre (K + 2) u sum|zbar w2|, +0.0 where h1 <= 0; the w2 and w1t
+ * rows of an item with n_j entries (n_j + 2) u and (n_j + 3) u sum|terms|.  D: h1 (K + 2) u, h2 (512 + 8) u, the logit (128 + 8) u
+ * (sum|terms| + |bias|); p additionally (T + 2) u p; from p, rowloss within (T + 2) u relative plus u / n_side (the rounding of
+ * 1 - p) and dlogit within 10 u relative; dz2 one product:
+ * bits; dz1 (128 + 2) u, dinB (512 + 8) u, W2-bar and w3-bar (n + 2) u, an item's w1t row (n_j + 2) u sum|terms|.
+ * Bit-exact orders (additions only, nothing to contract): the b2, min_boundary and interval_lengths gradients (a chain over the
+ * item's list; per entry ((bbar0 + bbar1) + bbar2) + bbar3 and its tails), G's b1-bar (dpre over the rows in row order), D's b1, b2
+ * and b3 gradients (rows in row order), and loss[0] of both entries (256 strided partials, then the halving tree).
+ * A stored entry with x <= 0 gets a, cls and zero value like any other, contributes to norm and h1, and takes no part in mode 1:
+ * its eloss, zbar and bbar are zero and scale does not count it; in mode 0 its dvalue is ignored.  Empty rows are allowed
+ * everywhere (G: h1 = relu(b1), norm = 1e-12f; D: h1 = relu(b1)).  A call on rows rowptr[0 .. n_rows] writes a, cls, value, zbar,
+ * bbar, eloss only at entries rowptr[0] .. rowptr[n_rows] - 1 and norm, h1, dpre only at rows 0 .. n_rows - 1, dinB only at B's
+ * entries; everything outside is untouched.  ggrad and dgrad are written in full: items no listed entry touches, the hidden padding
+ * lanes 125 .. 127, interval lengths <= 0 and units behind a closed relu get +0.0.  With p saturated to exactly 0 or 1 the row loss
+ * is 0 or 100 / n_side (nn.BCELoss's clamp) and dlogit is 0.  A refused call (RK_EINVAL) has launched and written nothing;
+ * rk_ap_g_forward with n_rows == 0 is an empty call (RK_OK); nA == 0 or nB == 0 (not both) and dgrad == NULL or dinB == NULL are
+ * forms of rk_ap_d_step, the absent side's pointers and the lists may then be NULL. */
 
 #ifdef __cplusplus
 }
