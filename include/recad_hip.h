@@ -886,6 +886,82 @@ int rk_ials_objective(int32_t n_rows, int32_t n_cols, int32_t d, const int32_t *
 int rk_slim_fit(int32_t n_items, const float *G /*[I*I]*/, float l1, int32_t sweeps, float *W /*[I*I]*/,
                 int32_t *info /*[3*I] or NULL*/, float *R_out /*[I*I] or NULL*/, int32_t *status /*int32[2]*/, void *stream);
 
+/* ---------------------------------------------------------------- APR victim --------- */
+/* Adversarial Personalized Ranking (He, He, Du and Chua, SIGIR 2018, "Adversarial Personalized Ranking for Recommendation"):
+ * matrix factorisation under the BPR loss with a second BPR term evaluated at the embeddings moved by the worst-case
+ * perturbation of size eps.  With adv_reg = 0 it is plain BPR-MF.  It has no counterpart in the reference; the definition is this:
+ *   tables: P [U, d] and Q [I, d], fp32, ONE [N = U + I, d] allocation, users first; item i is row U + i;
+ *   a step is a minibatch of B triplets (u_b, i_b, j_b) = (user, positive, negative), the sign convention of rk_bpr_rows;
+ *   1. data term: x_b = <p_u, q_j> - <p_u, q_i>; c_b = sigma(x_b) / B; L = (1 / B) sum_b softplus(x_b);
+ *      R = (lambda / 2B) sum_b (|p_u|^2 + |q_i|^2 + |q_j|^2);
+ *   2. Gamma, the gradient of L alone (not of R): row r sums its incidences in ascending order of 3 b + role (role 0 = user,
+ *      1 = positive, 2 = negative): Gamma_P[u] = sum c_b (q_j - q_i); Gamma_Q[i] = sum_{b: i_b = i} (-c_b p_u) +
+ *      sum_{b: j_b = i} (c_b p_u).  An item that is positive in some triplets and negative in others has ONE row;
+ *   3. perturbation, per row: n_r = sqrt(sum_k Gamma_rk^2); s_r = eps / max(n_r, 1e-12f), and s_r = 0 when n_r == 0;
+ *      Delta_rk = Gamma_rk * s_r.  A row whose Gamma is all zero gets exact zeros, whatever eps is.  Delta is a constant of the step: nothing is differentiated through it;
+ *   4. adversarial term: p' = p_u + Delta_P[u], q'_i = q_i + Delta_Q[i], q'_j = q_j + Delta_Q[j];
+ *      x'_b = <p', q'_j> - <p', q'_i>; c'_b = sigma(x'_b) / B; L' = (1 / B) sum_b softplus(x'_b);
+ *   5. the gradient of L + adv_reg L' + R: row r adds, per incidence and in the same order, (a) the term of step 2, (b) adv_reg
+ *      times the same term formed from c' and the moved partner rows, (c) (lambda / B) * its own row;
+ *   6. update: dense torch.optim.Adam over all N rows (untouched rows have g = 0 and their moments still decay), the
+ *      arithmetic of rk_adam_step.
+ *   Rounding: in steps 2 and 5 every product and every addition is fp32 and rounded on its own, in the written order, from
+ *   +0.0f: a term is fl(c * fl(q_j - q_i)), fl((-c) * p_u) or fl(c * p_u); the moved rows are fl(q + Delta); (b) is
+ *   fl(adv_reg * term'); (c) is fl(fl(lambda / (float) B) * self).  The dots, sigma(x) / B, softplus and the loss sums are worked out in double from the
+ *   fp32 rows and rounded once: x and c are the fp32 values nearest to them; the norms use a fixed fp32 tree.  Nothing adds
+ *   floats atomically: the same call gives the same bits.
+ *   Switches: with adv_reg == 0 steps 2-4 are not run (their workspace areas are not written, (b) is not added, L' = 0); with
+ *   eps == 0, Delta = 0 and L' = L.
+ * B is `batch` for every step but the last, which has n - (n_steps - 1) * batch triplets and divides by that.
+ * recad_amd/victim/apr.py drives the entries.  All pointers but the layout and the descriptor are device pointers. */
+#define RK_APR_MAX_DIM 256
+#define RK_APR_MAX_BATCH 65536
+/* status[0] of rk_apr_train_epoch (the numbering continues RK_SLIM_*); status[1] is the lowest offending triplet */
+#define RK_APR_BAD_USER 9     /* users[t] outside [0, n_users) */
+#define RK_APR_BAD_POS 10     /* pos[t] outside [0, n_items) */
+#define RK_APR_BAD_NEG 11     /* neg[t] outside [0, n_items) */
+/* Byte offsets of the workspace's areas (each a multiple of 256, and 256 bytes that nothing writes follow every area).  nb = min(batch, n) is the longest step, T = 3 * nb the most
+ * rows a step can touch.  Areas of ONE step, overwritten by the next: x, c, x_adv, c_adv (float [nb]); slot_of (int32 [T]:
+ * the slot of the row of incidence 3 b + role); gamma, delta (float [T * dim], row `slot`); norm (float [T]); part (double
+ * [3 * part_blocks]: the workgroups' partial sums of softplus(x), of the squared norms and of softplus(x')).  Areas of the
+ * epoch: keys (uint64 [3 n], the sorted plan: step << 44 | row << 20 | 3 b + role; step s owns [3 s batch, 3 s batch + 3 nb_s)),
+ * keys_in and sort_tmp (the sort's input and scratch), run (int32 [n_steps * run_stride]: per step {n_runs, start_0 ..
+ * start_{n_runs}}: slot k is the run of sorted positions [start_k, start_{k+1}) of its step, start_{n_runs} = 3 nb_s),
+ * grad (float [N * dim]: the dense gradient of the step, all zero between steps). */
+typedef struct rk_apr_layout {
+    int64_t bytes;
+    int64_t keys, keys_in, sort_tmp, sort_tmp_bytes, run, x, c, slot_of, gamma, norm, delta, x_adv, c_adv, part, grad;
+    int32_t run_stride, part_blocks, max_rows, n_steps;
+} rk_apr_layout;
+typedef struct rk_apr_desc {
+    int32_t n_users, n_items, dim, reserved0;
+    float *table;             /* [N * dim], users first */
+    float *m, *v;             /* Adam moments [N * dim] */
+    float *grad;              /* [N * dim] or NULL: receives the dense gradient of the LAST step */
+    float lam, eps, adv_reg, lr, beta1, beta2, adam_eps;
+    int32_t reserved1;
+    void *workspace;
+    int64_t workspace_bytes;
+} rk_apr_desc;
+/* *out = the layout for an epoch of n triplets in steps of `batch`.  Host only, nothing launched.  RK_EINVAL: a size < 1, dim
+ * above RK_APR_MAX_DIM, batch above RK_APR_MAX_BATCH, 2^20 steps or more, 2^24 rows or more, n of 2^31 / 3 or more, no `out`. */
+int rk_apr_workspace(int32_t n_users, int32_t n_items, int32_t dim, int64_t n, int32_t batch, rk_apr_layout *out);
+/* One epoch: ceil(n / batch) steps as defined, Adam steps adam_t0 + 1 ...  The ids are validated first by a kernel that reads
+ * nothing else, and status (device, int32[2]) is read back, which is the call's only synchronisation: {0, -1} without a
+ * violation; with one RK_EINVAL, status = {RK_APR_BAD_*, lowest such triplet} and nothing else is launched or written.  Then
+ * the plan (keys, one radix sort, the run table) once, and per step five launches: apr_coef_kernel<VEC4, ADV = 0> (x, c, partial sums),
+ * apr_rows_kernel<GRAD = 0, REGS> (one wave per touched row: Gamma, n, Delta, slot_of), apr_coef_kernel<VEC4, ADV = 1> (x', c'),
+ * apr_rows_kernel<GRAD = 1, REGS> (one wave per touched row: the row of step 5 into the dense gradient) and apr_adam_kernel,
+ * the Adam pass over all N * dim elements, which stores 0
+ * in place of every gradient it reads, copies it to desc->grad when that is given, updates only with apply_update != 0, and
+ * writes losses[3 s .. 3 s + 2] = {L, L', R} of step s (device, double, summed in a fixed order).
+ * RK_EINVAL with nothing launched and nothing written: dim outside 1..RK_APR_MAX_DIM, batch outside 1..RK_APR_MAX_BATCH,
+ * n <= 0, eps or adv_reg negative or not finite, adam_t0 < 0, a workspace smaller than rk_apr_workspace says or not
+ * aligned to 256 bytes, a missing pointer, apply_update == 0 without desc->grad, the limits of rk_apr_workspace. */
+int rk_apr_train_epoch(const rk_apr_desc *desc, const int64_t *users, const int64_t *pos, const int64_t *neg, int64_t n,
+                       int32_t batch, int32_t adam_t0, int32_t apply_update, double *losses /*[3*n_steps]*/,
+                       int32_t *status /*int32[2]*/, void *stream);
+
 /* ---------------------------------------------------------------- attacker --------- */
 /* AUSH (recad/model/attacker/aush.py, registry recad/default.py:159-168) without the dense U x I train_mat
  * (explicit.py:102,134-143) and the dense B x I batches (explicit.py:178-199, aush.py:92-134): each attack row is the sparse

@@ -27,6 +27,9 @@ RK_EASE_MAX_ITEMS, RK_EASE_BLOCK_SMALL, RK_EASE_BLOCK_LARGE = 65536, 32, 64
 RK_EASE_BAD_GRAM, RK_EASE_NOT_SPD = 5, 6
 RK_IALS_MAX_DIM, RK_IALS_CHUNK, RK_IALS_GRAM_ROWS, RK_IALS_NOT_SPD = 128, 64, 256, 7
 RK_SLIM_MAX_ITEMS, RK_SLIM_BAD_DIAG = 20464, 8
+RK_APR_MAX_DIM, RK_APR_MAX_BATCH = 256, 65536
+RK_APR_RULES = {9: "a user id outside [0, n_users)", 10: "a positive item id outside [0, n_items)",
+                11: "a negative item id outside [0, n_items)"}
 
 
 class HipLibraryMissing(RuntimeError):
@@ -176,6 +179,27 @@ class AiaDesc(C.Structure):
     ]
 
 
+class AprLayout(C.Structure):
+    """rk_apr_layout (include/recad_hip.h): byte offsets of the workspace's areas."""
+
+    AREAS = ("keys", "keys_in", "sort_tmp", "sort_tmp_bytes", "run", "x", "c", "slot_of", "gamma", "norm", "delta", "x_adv", "c_adv",
+             "part", "grad")
+    _fields_ = [("bytes", C.c_int64)] + [(k, C.c_int64) for k in AREAS] + [
+        ("run_stride", C.c_int32), ("part_blocks", C.c_int32), ("max_rows", C.c_int32), ("n_steps", C.c_int32)]
+
+
+class AprDesc(C.Structure):
+    """rk_apr_desc (include/recad_hip.h)."""
+
+    _fields_ = [
+        ("n_users", C.c_int32), ("n_items", C.c_int32), ("dim", C.c_int32), ("reserved0", C.c_int32),
+        ("table", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad", C.c_void_p),
+        ("lam", C.c_float), ("eps", C.c_float), ("adv_reg", C.c_float), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+        ("adam_eps", C.c_float), ("reserved1", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
 RK_AIA_MAX_BATCH = 256
 RK_AUSH_HG, RK_AUSH_HD = 128, 150
 RK_AUSH_MAX_FILLER, RK_AUSH_MAX_SELECT, RK_AUSH_MAX_PAIRS = 256, 16, 4096
@@ -270,6 +294,8 @@ _SIGNATURES = {
     "rk_ials_half_sweep": [_I32, _I32, _I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P],
     "rk_ials_objective": [_I32, _I32, _I32, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P],
     "rk_slim_fit": [_I32, _P, _F, _I32, _P, _P, _P, _P, _P],
+    "rk_apr_workspace": [_I32, _I32, _I32, _I64, _I32, C.POINTER(AprLayout)],
+    "rk_apr_train_epoch": [C.POINTER(AprDesc), _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
     "rk_aush_workspace_bytes": [_I32, _I32, _I32, C.POINTER(_I64)],
     "rk_aush_eligible": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, C.POINTER(_I32), _P],
     "rk_aush_permute": [_I32, _P, C.c_uint64, C.c_uint64, _P, _P],

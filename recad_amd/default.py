@@ -34,6 +34,10 @@ MODEL = {
         # build-specific (no reference counterpart): sparse linear item-item weights by coordinate descent (Ning and Karypis 2011),
         # victim/slim.py; l2_reg is the constant added to the Gram matrix's diagonal
         "slim": {"l1_reg": 1.0, "l2_reg": 5.0, "sweeps": 50},
+        # build-specific (no reference counterpart): adversarially trained BPR-MF (He, He, Du and Chua 2018), victim/apr.py;
+        # adv_reg = 0 is plain BPR-MF; the adversarial term is switched on after adv_start_epoch of the victim's own epochs
+        "apr": {"factor_num": 64, "reg_lambda": 1e-4, "eps": 0.5, "adv_reg": 1.0, "adv_start_epoch": 200, "init_std": 0.01,
+                "optim": "adam", "lr": 1e-3},
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},

@@ -1,3 +1,4 @@
+from .apr import APR
 from .base import BaseVictim
 from .ease import EASE
 from .ials import IALS
@@ -7,4 +8,4 @@ from .mf import MF
 from .ncf import NCF
 from .slim import SLIM
 
-__all__ = ["BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "NCF", "SLIM"]
+__all__ = ["APR", "BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "NCF", "SLIM"]
