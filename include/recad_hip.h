@@ -962,6 +962,108 @@ int rk_apr_train_epoch(const rk_apr_desc *desc, const int64_t *users, const int6
                        int32_t batch, int32_t adam_t0, int32_t apply_update, double *losses /*[3*n_steps]*/,
                        int32_t *status /*int32[2]*/, void *stream);
 
+/* ---------------------------------------------------------------- Mult-VAE victim --------- */
+/* Mult-VAE (Liang, Krishnan, Hoffman and Jebara, WWW 2018, "Variational Autoencoders for Collaborative Filtering"): a
+ * variational autoencoder over a user's row of the implicit matrix with a multinomial likelihood over the whole catalogue and
+ * an annealed KL term.  It has no per-user parameters and no counterpart in the reference; the definition is this:
+ *   parameters, fp32, in ONE flat buffer in this order (rk_mvae_layout gives the element offsets), so that Adam is one launch:
+ *     W1 [I, H] (one row per item: the sparse layer gathers rows), b1 [H]; W2 [2L, H], b2 [2L]; W3 [H, L], b3 [H];
+ *     W4 [I, H], b4 [I].  Apart from W1 every weight is stored out x in: the forward products read both operands k-contiguous.
+ *   chain(x, W)[u, j] means s = 0; s = fmaf(x[u, k], W[j, k], s) for k ascending: what the whole-K fp32 MFMA GEMM computes, to
+ *   the bit; a bias is added afterwards by one fp32 add.
+ *   A step works on B users (batch positions 0 .. B - 1, ids may repeat) each with n_u >= 1 stored entries; x_ui = 1 for a
+ *   stored entry whatever its value.  `step` is the count of updates so far (step0 + the step's index in the epoch).
+ *   1. input: s_u = n_u^-1/2; with S = rk_drop_step_seed of (seed, step) and S_u = rk_drop_step_seed of (S, u), entry (u, i) is
+ *      kept iff rk_drop_keep says so for (S_u, i, thresh24) (csrc/common.h), thresh24 = (unsigned)((1 - dropout) * 2^24) with 1 - dropout formed in double from the fp32 dropout;
+ *      c_u = s_u / (1 - dropout), in double (1 / sqrt(n_u), then the division), rounded once.  dropout = 0 keeps every entry;
+ *   2. sparse layer: a_uh = sum of W1[i, h] over the kept items of row u in ascending item order, fp32 adds from +0.0;
+ *      pre1 = fl(fl(c_u * a_uh) + b1[h]); h1 = tanh(pre1) evaluated in double, rounded once;
+ *   3. encoder head: ml = chain(h1, W2) + b2, [B, 2L]; mu = ml[:, :L], logvar = ml[:, L:];
+ *   4. sample: with E = rk_drop_step_seed of (seed ^ 0xA5A5A5A5A5A5A5A5, step), E_u = rk_drop_step_seed of (E, u) and
+ *      r_t = rk_mix64 of (E_u ^ t * 0xD1342543DE82EF95) (64-bit wrap), u1 = ((r_{2j} >> 11) + 1) * 2^-53, u2 = (r_{2j+1} >> 11) * 2^-53,
+ *      eps[u, j] = sqrt(-2 ln u1) * cos(2 pi u2) in double, rounded once; z = mu + eps * exp(logvar / 2) in double from the
+ *      fp32 mu, eps and logvar, rounded once; KL_u = -1/2 sum_j (1 + logvar - mu^2 - exp(logvar)) in double;
+ *   5. decoder: pre2 = chain(z, W3) + b3; h2 = tanh(pre2) as in 2; logits = chain(h2, W4) + b4, [B, I];
+ *   6. loss, one pass per logits row and in place: lse_u = max + ln(sum_i exp(l_ui - max)) in double; nll_u = sum over ALL the
+ *      row's stored items (dropout is on the input only) of (lse_u - l_ui); loss = (1 / B) sum_u (nll_u + beta KL_u), reported
+ *      with (1 / B) sum nll and (1 / B) sum KL; dl[u, i] = ((n_u exp(l_ui - lse_u) - x_ui) / B) in double, rounded once,
+ *      written over the logits; beta = min(anneal_cap, step / total_anneal_steps) in double (anneal_cap when total_anneal_steps
+ *      is 0).  B is the number of rows of this step: a short last step divides by its own size;
+ *   7. backward, every product a chain over the summed index in ascending order: gW4 = chain_u(dl, h2); gb4 = the column sums
+ *      of dl by fp32 adds in ascending batch position (so are gb3 of dp2, gb2 of dml, gb1 of dp1); dh2 = chain_i(dl, W4);
+ *      dp2 = fl(dh2 * fl(1 - fl(h2 * h2))); gW3 = chain_u(dp2, z); dz = chain_h(dp2, W3); dmu = dz + (beta / B) mu and
+ *      dlogvar = 1/2 dz eps exp(logvar / 2) + (beta / 2B) (exp(logvar) - 1), each in double and rounded once, dml = [dmu |
+ *      dlogvar]; gW2 = chain_u(dml, h1); dh1 = chain_j(dml, W2); dp1 as dp2; gW1[i, h]: acc = +0.0, then acc = fmaf(c_u,
+ *      dp1[u, h], acc) over the batch positions that hold i as a KEPT entry, ascending; an item without one gets +0.0;
+ *   8. update: torch.optim.Adam over the flat buffer, the arithmetic of rk_adam_step, Adam step number step + 1.
+ *   The sums of exp, nll and KL run in fixed trees (tests hold them to rounding budgets); nothing adds floats atomically and
+ *   the item-grouped view of the kept entries is built once per step by one radix sort of (item << 12 | batch position): the
+ *   same call gives the same bits.
+ *   Inference: no dropout (c_u = s_u, and 0 for a user without entries), z = mu, and only the first L rows of W2 are multiplied.
+ *   Every product is whole-K at every catalogue size (DESIGN 16 records the price at the largest shape).
+ * recad_amd/victim/multvae.py drives the entries.  All pointers but the layout and the descriptor are device pointers. */
+#define RK_MVAE_MAX_HIDDEN 1024
+#define RK_MVAE_MAX_LATENT 512
+#define RK_MVAE_MAX_BATCH 4096
+#define RK_MVAE_MAX_ITEMS 262144  /* the row kernel's LDS bitmap: 32 KiB; batch * n_items stays below 2^31 */
+/* status[0] of the rk_mvae_* entries (the numbering continues RK_APR_*); status[1] is the lowest offending position */
+#define RK_MVAE_BAD_USER 12   /* user_ids[t] outside [0, n_users) */
+#define RK_MVAE_BAD_ROW 13    /* the row of user_ids[t] is not strictly ascending inside [0, n_items) */
+#define RK_MVAE_EMPTY_ROW 14  /* user_ids[t] has no stored entry (training only) */
+#define RK_MVAE_NNZ_CAP 15    /* step status[1] holds more entries than the workspace's nnz_cap */
+#define RK_MVAE_BAD_ITEM 16   /* item_ids[t] outside [0, n_items) (rk_mvae_pair_scores) */
+/* Byte offsets of the workspace's areas (each a multiple of 256, and 256 bytes that nothing writes follow every area), all of
+ * ONE step and overwritten by the next; B = batch, E = nnz_cap, the most stored entries a step may hold.  brp (int32 [B + 1]:
+ * prefix sums of the rows' lengths); keep (int32 [E]: entry brp[b] + k is the k-th stored item of batch row b, 1 = kept); keys_in,
+ * keys (the sort's input and output; its scratch is allocated on the stream); t_ptr (int32 [I + 1]) and t_row (int32 [E]): item i's kept batch
+ * positions are t_row[t_ptr[i] .. t_ptr[i + 1]), ascending; c (float [B]); a, pre1, h1, pre2, h2, dh2, dp2, dh1, dp1 (float
+ * [B * H]); ml, dml (float [B * 2L]); eps, z, dz (float [B * L]); kl, lse, nll (double [B]); logits (float [B * I], holds dl
+ * after the step); grad (float [n_params], the flat gradient in the parameters' order).  w1 .. b4 and n_params are ELEMENT
+ * offsets into the flat parameter buffer, not workspace areas. */
+typedef struct rk_mvae_layout {
+    int64_t bytes;
+    int64_t brp, keep, keys, keys_in, t_ptr, t_row, c, a, pre1, h1, ml, eps, z, kl, pre2, h2, logits, lse, nll,
+        dh2, dp2, dz, dml, dh1, dp1, grad;
+    int64_t w1, b1, w2, b2, w3, b3, w4, b4, n_params;
+    int64_t nnz_cap;
+    int32_t batch, reserved;
+} rk_mvae_layout;
+typedef struct rk_mvae_desc {
+    int32_t n_users, n_items, hidden, latent;
+    const int32_t *rowptr, *col;   /* the rating CSR, [n_users + 1] and [nnz]; values are not read */
+    float *params, *m, *v;         /* the flat buffer and its Adam moments, [n_params]; m, v may be NULL for scoring */
+    float *grad;                   /* [n_params] or NULL: receives the gradient of the LAST step when apply_update == 0 */
+    float *logits_out;             /* [batch * n_items] or NULL: a copy of the LAST step's logits before dl overwrites them */
+    float dropout, anneal_cap, lr, beta1, beta2, adam_eps;
+    int64_t total_anneal_steps;
+    uint64_t seed;
+    int64_t ws_nnz_cap;            /* the (batch, nnz_cap) the workspace was laid out for */
+    int32_t ws_batch, reserved;
+    void *workspace;
+    int64_t workspace_bytes;
+} rk_mvae_desc;
+/* *out = the layout for steps of up to `batch` users holding up to nnz_cap stored entries.  Host only, nothing launched.
+ * RK_EINVAL: n_items outside 1..RK_MVAE_MAX_ITEMS, hidden outside 1..RK_MVAE_MAX_HIDDEN, latent outside 1..RK_MVAE_MAX_LATENT,
+ * batch outside 1..RK_MVAE_MAX_BATCH, nnz_cap outside 1..2^31 - 1, no `out`. */
+int rk_mvae_workspace(int32_t n_items, int32_t hidden, int32_t latent, int32_t batch, int64_t nnz_cap, rk_mvae_layout *out);
+/* One epoch over user_ids[0 .. n): ceil(n / batch) steps as defined, the first with step = step0; every stage of the LAST step
+ * stays readable in the workspace.  A check kernel that reads only the ids and the rating rows runs first and status (device,
+ * int32[2]) is read back, the call's only synchronisation: {0, -1} without a violation; with one RK_EINVAL, status =
+ * {RK_MVAE_*, lowest offending position (or step)} and nothing else is launched or written.  losses[3 s .. 3 s + 2] = {loss,
+ * mean nll, mean KL} of step s (device, double).  With apply_update == 0 the parameters and moments are not touched and
+ * desc->grad receives the gradient.  RK_EINVAL with nothing launched and nothing written: the limits of rk_mvae_workspace, a
+ * workspace smaller than its layout or not aligned to 256 bytes, batch above ws_batch, n < 1, step0 < 0, dropout outside
+ * [0, 1), anneal_cap negative or not finite, a missing pointer, apply_update == 0 without desc->grad. */
+int rk_mvae_train_epoch(const rk_mvae_desc *desc, const int32_t *user_ids, int64_t n, int32_t batch, int64_t step0,
+                        int32_t apply_update, double *losses /*[3*n_steps]*/, int32_t *status /*int32[2]*/, void *stream);
+/* out[r * ldo + i] = the inference logit of item i for user_ids[r], r < nb, seen items included, written by the GEMM's
+ * epilogue in blocks of ws_batch rows.  The ids are range-checked first (one synchronisation); a bad one is RK_EINVAL. */
+int rk_mvae_scores(const rk_mvae_desc *desc, const int32_t *user_ids, int32_t nb, float *out, int64_t ldo, void *stream);
+/* out[q] = the inference logit of (user_ids[q], item_ids[q]), q < n: the same chain order, so a pair equals the entry of
+ * rk_mvae_scores to the bit.  n == 0 does nothing; ids outside the tables are RK_EINVAL. */
+int rk_mvae_pair_scores(const rk_mvae_desc *desc, const int32_t *user_ids, const int32_t *item_ids, int64_t n, float *out,
+                        void *stream);
+
 /* ---------------------------------------------------------------- attacker --------- */
 /* AUSH (recad/model/attacker/aush.py, registry recad/default.py:159-168) without the dense U x I train_mat
  * (explicit.py:102,134-143) and the dense B x I batches (explicit.py:178-199, aush.py:92-134): each attack row is the sparse

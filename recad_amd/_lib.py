@@ -200,6 +200,35 @@ class AprDesc(C.Structure):
     ]
 
 
+class MvaeLayout(C.Structure):
+    """rk_mvae_layout (include/recad_hip.h): byte offsets of the workspace's areas, element offsets of the parameters."""
+
+    AREAS = ("brp", "keep", "keys", "keys_in", "t_ptr", "t_row", "c", "a", "pre1", "h1", "ml", "eps", "z", "kl",
+             "pre2", "h2", "logits", "lse", "nll", "dh2", "dp2", "dz", "dml", "dh1", "dp1", "grad")
+    PARAMS = ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")
+    _fields_ = [("bytes", C.c_int64)] + [(k, C.c_int64) for k in AREAS] + [(k, C.c_int64) for k in PARAMS] + [
+        ("n_params", C.c_int64), ("nnz_cap", C.c_int64), ("batch", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MvaeDesc(C.Structure):
+    """rk_mvae_desc (include/recad_hip.h)."""
+
+    _fields_ = [
+        ("n_users", C.c_int32), ("n_items", C.c_int32), ("hidden", C.c_int32), ("latent", C.c_int32),
+        ("rowptr", C.c_void_p), ("col", C.c_void_p),
+        ("params", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad", C.c_void_p), ("logits_out", C.c_void_p),
+        ("dropout", C.c_float), ("anneal_cap", C.c_float), ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+        ("adam_eps", C.c_float),
+        ("total_anneal_steps", C.c_int64), ("seed", C.c_uint64), ("ws_nnz_cap", C.c_int64),
+        ("ws_batch", C.c_int32), ("reserved", C.c_int32),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
+RK_MVAE_MAX_HIDDEN, RK_MVAE_MAX_LATENT, RK_MVAE_MAX_BATCH, RK_MVAE_MAX_ITEMS = 1024, 512, 4096, 262144
+RK_MVAE_RULES = {12: "a user id outside [0, n_users)", 13: "a row whose item ids are not strictly ascending inside [0, n_items)",
+                 14: "a user without a train item", 15: "a step with more entries than the workspace's nnz_cap",
+                 16: "an item id outside [0, n_items)"}
 RK_AIA_MAX_BATCH = 256
 RK_AUSH_HG, RK_AUSH_HD = 128, 150
 RK_AUSH_MAX_FILLER, RK_AUSH_MAX_SELECT, RK_AUSH_MAX_PAIRS = 256, 16, 4096
@@ -296,6 +325,10 @@ _SIGNATURES = {
     "rk_slim_fit": [_I32, _P, _F, _I32, _P, _P, _P, _P, _P],
     "rk_apr_workspace": [_I32, _I32, _I32, _I64, _I32, C.POINTER(AprLayout)],
     "rk_apr_train_epoch": [C.POINTER(AprDesc), _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
+    "rk_mvae_workspace": [_I32, _I32, _I32, _I32, _I64, C.POINTER(MvaeLayout)],
+    "rk_mvae_train_epoch": [C.POINTER(MvaeDesc), _P, _I64, _I32, _I64, _I32, _P, _P, _P],
+    "rk_mvae_scores": [C.POINTER(MvaeDesc), _P, _I32, _P, _I64, _P],
+    "rk_mvae_pair_scores": [C.POINTER(MvaeDesc), _P, _P, _I64, _P, _P],
     "rk_aush_workspace_bytes": [_I32, _I32, _I32, C.POINTER(_I64)],
     "rk_aush_eligible": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, C.POINTER(_I32), _P],
     "rk_aush_permute": [_I32, _P, C.c_uint64, C.c_uint64, _P, _P],

@@ -38,6 +38,10 @@ MODEL = {
         # adv_reg = 0 is plain BPR-MF; the adversarial term is switched on after adv_start_epoch of the victim's own epochs
         "apr": {"factor_num": 64, "reg_lambda": 1e-4, "eps": 0.5, "adv_reg": 1.0, "adv_start_epoch": 200, "init_std": 0.01,
                 "optim": "adam", "lr": 1e-3},
+        # build-specific (no reference counterpart): the multinomial variational autoencoder (Liang et al. 2018), victim/multvae.py;
+        # seed None = the initialisation's and the device RNG's seed is drawn from torch's global RNG at .I()
+        "multvae": {"hidden_dim": 600, "latent_dim": 200, "dropout": 0.5, "anneal_cap": 0.2, "total_anneal_steps": 200000,
+                    "batch_size": 500, "optim": "adam", "lr": 1e-3, "seed": None},
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},

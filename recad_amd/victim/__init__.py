@@ -5,7 +5,8 @@ from .ials import IALS
 from .itemknn import ItemKNN
 from .lightgcn import LightGCN
 from .mf import MF
+from .multvae import MultVAE
 from .ncf import NCF
 from .slim import SLIM
 
-__all__ = ["APR", "BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "NCF", "SLIM"]
+__all__ = ["APR", "BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "MultVAE", "NCF", "SLIM"]
