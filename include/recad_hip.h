@@ -649,6 +649,71 @@ int rk_knn_degsim(int32_t n_users, int32_t n_items, const int32_t *rowptr, const
  * and 0.0 are equal).  The radix sort of rk_pca_select.  Synchronous; RK_EINVAL on a non-finite score or m outside 0..n. */
 int rk_knn_select(int32_t n, const float *score, int32_t m, int32_t largest, int32_t *order_out, void *stream);
 
+/* CatchSyncSelectUsers: synchronicity and normality of a user's items over a grid of item features (Jiang, Cui, Beutel,
+ * Faloutsos, Yang, "CatchSync: Catching Synchronized Behavior in Large Directed Graphs", KDD 2014), integer-exact and
+ * repeatable.  It has no counterpart in the reference; the definition is this:
+ *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending); after
+ *   validation the values are ignored, every stored entry is an edge;
+ *   d_u = the length of row u; deg_i = the length of column i; reach_i = sum over the users u of column i of d_u (the
+ *   un-normalised HITS authority after one step from the all-ones hub vector); reach_i <= nnz < 2^31;
+ *   bucket(x, s) for an integer x >= 1 and s = grid_bits in 0..3: e = the index of x's leading one bit, m = the s bits directly
+ *   below that bit (zero-filled when e < s), bucket = e * 2^s + m: shifts and masks only, no logarithm;
+ *   for every rated item (deg_i >= 1): key_i = bucket(deg_i, s) * 65536 + bucket(reach_i, s); the distinct keys in ascending
+ *   order are the cells 0 .. M - 1; cell_of[i] = the item's cell, -1 for an unrated item; N_c = the items of cell c;
+ *   N = sum N_c, SB = sum N_c^2, all_equal = 1 when every N_c is the same (M <= 1 included), else 0;
+ *   M <= RK_CS_MAX_CELLS and I < RK_CS_MAX_ITEMS = 2^26 (so d * N and d^2 stay below 2^53), more is refused;
+ *   n_uc = the number of u's items in cell c; pair_num[u] = sum_c n_uc^2 (the ordered pairs of u's items that share a cell, self
+ *   pairs included); back_num[u] = sum_c n_uc N_c = the sum over u's items of N_cell(i), both int64; an entry whose cell_of is
+ *   -1 or >= M is skipped (no real graph has one; it keeps a caller's table from indexing outside LDS);
+ *   scores, each formed in fp64 from those integers with the operations in the written order and no contraction, rounded once
+ *   to fp32; d = d_u; a user with d < min_items (min_items >= 2) gets exactly -1.0f, below every eligible score;
+ *     sync:      (pair_num - d) / (d * (d - 1)), the share of distinct item pairs inside one cell;
+ *     normality: back_num / (d * N);
+ *     residual:  sy - s_min, sy = pair_num / (d * d), n = back_num / (d * N), s_b = SB / (N * N),
+ *                s_min = (((M * n) * n - 2 * n) + s_b) / (M * s_b - 1), the least sum p_c^2 under sum p_c = 1 and
+ *                sum p_c N_c / N = n (the paper's lower limit of synchronicity at a given normality); with all_equal the
+ *                denominator is zero in exact arithmetic, that case is decided on the integers and s_min = 1 / M;
+ *   flagged: the flag_count(attack_num, U) users of LARGEST score, ties to the lower id (rk_knn_select with largest = 1).
+ * Not built: the converged HITS authority as second feature, the paper's per-bin 3-sigma rule, scoring items.
+ * recad_amd/defense/catchsync_select_users.py drives these entries.  All pointers are device pointers. */
+#define RK_CS_MAX_CELLS 8192
+#define RK_CS_MAX_ITEMS (1 << 26)
+/* status[0] of rk_cs_cells (the numbering continues RK_MVAE_*) */
+#define RK_CS_BAD_FEATURE 17     /* a negative deg_item or reach, or reach 0 at a rated item (bucket needs x >= 1) */
+#define RK_CS_TOO_MANY_CELLS 18  /* reported at the lowest item whose cell index would be >= RK_CS_MAX_CELLS */
+#define RK_CS_FORM_AUTO 0        /* rows of up to 512 items by one wave, longer ones by the workgroup */
+#define RK_CS_FORM_WAVE 1
+#define RK_CS_FORM_WORKGROUP 2
+#define RK_CS_SCORE_SYNC 0
+#define RK_CS_SCORE_NORMALITY 1
+#define RK_CS_SCORE_RESIDUAL 2
+/* deg_item and reach of every item from the CSR's row pointers and the transpose colptr / crow that rk_pca_transpose writes.
+ * One wave per item, integer sums only.  Asynchronous. */
+int rk_cs_features(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *colptr, const int32_t *crow,
+                   int32_t *deg_item /*[I]*/, int32_t *reach /*[I]*/, void *stream);
+/* Keys, their ranking, counts and SB.  cell_count[c] = N_c for c < M and 0 beyond; info = {M, N, SB, all_equal}.  The arrays
+ * need not come from a graph.  Synchronous: reads status (device, int32[2]) back.  Without a violation status = {0, -1}.  With
+ * one: RK_EINVAL, status = {rule, item} of the lowest offending item (items that break RK_CS_BAD_FEATURE take no part in the
+ * ranking) and cell_of / cell_count / info are UNTOUCHED: they are formed in temporaries and copied on success.
+ * RK_EINVAL with nothing launched: grid_bits outside 0..3, n_items >= RK_CS_MAX_ITEMS, a missing pointer. */
+int rk_cs_cells(int32_t n_items, const int32_t *deg_item, const int32_t *reach, int32_t grid_bits, int32_t *cell_of /*[I]*/,
+                int32_t *cell_count /*[RK_CS_MAX_CELLS]*/, int64_t *info /*[4]*/, int32_t *status /*int32[2]*/, void *stream);
+/* pair_num and back_num of every user.  The per-user cell histogram is int32 in LDS, filled with integer LDS atomics; per user
+ * the row is walked three times (add 1 to each touched cell, read the counts back and sum them, zero the touched cells), so
+ * the histogram is cleared in full once per workgroup.  Two forms that give identical words: one wave per user, each of the four
+ * waves on its own M-word slice (16 * M bytes of LDS, 128 KiB at M = 8192), a workgroup serving 32 entries of `order`; one
+ * 256-thread workgroup per user (4 * M bytes), a workgroup serving 8 entries in turn.  Workgroup g of G takes the entries g,
+ * g + G, g + 2 G ...: a descending order spreads its long rows over all workgroups.  form: RK_CS_FORM_*.  order ([U] or
+ * NULL) as in rk_knn_degsim: results do not depend on it, an entry outside [0, U) is skipped.  No float, no global atomics.
+ * Asynchronous.  RK_EINVAL with nothing launched: M outside 1..RK_CS_MAX_CELLS, form outside 0..2, a missing pointer. */
+int rk_cs_user_sums(int32_t n_users, const int32_t *rowptr, const int32_t *col, const int32_t *cell_of, const int32_t *cell_count,
+                    int32_t n_cells, int32_t form, const int32_t *order /*[U] or NULL*/, int64_t *pair_num /*[U]*/,
+                    int64_t *back_num /*[U]*/, void *stream);
+/* score[u] by the formulas above; mode: RK_CS_SCORE_*.  Asynchronous.  RK_EINVAL with nothing launched: mode outside 0..2,
+ * min_items < 2, a missing pointer. */
+int rk_cs_scores(int32_t n_users, const int32_t *rowptr, const int64_t *pair_num, const int64_t *back_num, const int64_t *info,
+                 int32_t mode, int32_t min_items, float *score /*[U]*/, void *stream);
+
 /* ItemKNN victim: item-neighbourhood collaborative filtering (Sarwar et al. 2001; Deshpande and Karypis 2004), exact and
  * repeatable.  It has no counterpart in the reference; the definition is this:
  *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending);

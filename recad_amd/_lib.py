@@ -22,6 +22,10 @@ RK_RANK_MAX_NK = 8   # cut-offs per rk_rank_metrics call
 RK_KNN_MAX_K, RK_KNN_MAX_BAND = 128, 38720
 RK_KNN_RULES = {1: "a value that is not an integer in 1..127", 2: "column ids not strictly ascending inside [0, n_items)",
                 3: "a squared norm of 2^31 or more", 4: "row pointers that decrease or are negative"}
+RK_CS_MAX_CELLS, RK_CS_MAX_ITEMS = 8192, 1 << 26
+RK_CS_RULES = {17: "a negative deg_item or reach, or reach 0 at a rated item", 18: "more than RK_CS_MAX_CELLS cells"}
+RK_CS_FORM_AUTO, RK_CS_FORM_WAVE, RK_CS_FORM_WORKGROUP = 0, 1, 2
+RK_CS_SCORE_SYNC, RK_CS_SCORE_NORMALITY, RK_CS_SCORE_RESIDUAL = 0, 1, 2
 RK_ITEMKNN_MAX_BAND, RK_ITEMKNN_MAX_ITEMS, RK_ITEMKNN_MAX_USER_BLOCK = 39872, 163776, 16
 RK_EASE_MAX_ITEMS, RK_EASE_BLOCK_SMALL, RK_EASE_BLOCK_LARGE = 65536, 32, 64
 RK_EASE_BAD_GRAM, RK_EASE_NOT_SPD = 5, 6
@@ -309,6 +313,10 @@ _SIGNATURES = {
     "rk_knn_norms": [_I32, _I32, _P, _P, _P, _P, _P, _P],
     "rk_knn_degsim": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
     "rk_knn_select": [_I32, _P, _I32, _I32, _P, _P],
+    "rk_cs_features": [_I32, _I32, _P, _P, _P, _P, _P, _P],
+    "rk_cs_cells": [_I32, _P, _P, _I32, _P, _P, _P, _P, _P],
+    "rk_cs_user_sums": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
+    "rk_cs_scores": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P],
     "rk_itemknn_neighbors": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
     "rk_itemknn_scores": [_I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P],
     "rk_itemknn_pair_scores": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P],

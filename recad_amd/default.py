@@ -78,7 +78,11 @@ MODEL = {
     # recad/default.py:223-228; block / tol / max_iter / seed are this build's solver knobs (block None = 8, or 16 when kVals > 5)
     "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED},
                  # build-specific (no reference counterpart): DegSim neighbour detection, defense/knn_select_users.py
-                 "KnnSelectUsers": {"k": 25, "attack_num": 50, "select": "low", "band": None, "schedule": "work"}},
+                 "KnnSelectUsers": {"k": 25, "attack_num": 50, "select": "low", "band": None, "schedule": "work"},
+                 # build-specific (no reference counterpart): CatchSync synchronicity detection, defense/catchsync_select_users.py;
+                 # form None = automatic by row length
+                 "CatchSyncSelectUsers": {"score": "sync", "grid_bits": 1, "min_items": 20, "attack_num": 50, "schedule": "work",
+                                          "form": None}},
 }
 for _scope in MODEL.values():
     for _cfg in _scope.values():

@@ -1,4 +1,5 @@
+from .catchsync_select_users import CatchSyncSelectUsers
 from .knn_select_users import KnnSelectUsers
 from .pca_select_users import PCASelectUsers
 
-__all__ = ["KnnSelectUsers", "PCASelectUsers"]
+__all__ = ["CatchSyncSelectUsers", "KnnSelectUsers", "PCASelectUsers"]

@@ -8,7 +8,8 @@ factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": vic
              "attacker": {"aia": attack.AIA, "aush": attack.Aush, "aushplus": attack.AushPlus, "random": attack.RandomAttacker,
                           "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack,
                           "uba": attack.UBA},
-             "defender": {"PCASelectUsers": defense.PCASelectUsers, "KnnSelectUsers": defense.KnnSelectUsers}}
+             "defender": {"PCASelectUsers": defense.PCASelectUsers, "KnnSelectUsers": defense.KnnSelectUsers,
+                          "CatchSyncSelectUsers": defense.CatchSyncSelectUsers}}
 
 
 def from_config(scope, name, **kwargs):
