@@ -1026,6 +1026,33 @@ int rk_apr_workspace(int32_t n_users, int32_t n_items, int32_t dim, int64_t n, i
 int rk_apr_train_epoch(const rk_apr_desc *desc, const int64_t *users, const int64_t *pos, const int64_t *neg, int64_t n,
                        int32_t batch, int32_t adam_t0, int32_t apply_update, double *losses /*[3*n_steps]*/,
                        int32_t *status /*int32[2]*/, void *stream);
+/* One epoch of n_rep independent APR models ("members") in shared launches.  Definition: for every member r, table, m, v, desc.grad
+ * when given, losses[r] and status[2 r .. 2 r + 1] hold, bit for bit, what
+ *   rk_apr_train_epoch(&descs[r], users[r], pos[r], neg[r], n[r], batch, adam_t0[r], apply_update, losses[r], status + 2 r, stream)
+ * leaves on copies of the same inputs (the APR definition above), and so do the areas of the member's workspace.  Members may
+ * differ in n_users, n_items, n (so in their step counts), lam, eps, adv_reg, lr, the betas, adam_eps and adam_t0; each has its own
+ * workspace, sized by rk_apr_workspace; dim, batch and apply_update are common.  descs, n, adam_t0 and the four pointer arrays are
+ * HOST arrays of n_rep entries; what users[r], pos[r], neg[r] and losses[r] (double [3 * n_steps_r]) point to is on the device,
+ * as is status (int32 [2 * n_rep]).
+ * Launches: the ids of all members are validated by one launch and all status words are read back in one synchronisation, the
+ * only one of the call; with a bad id in any member RK_EINVAL, status of member r = {RK_APR_BAD_*, lowest such triplet} or
+ * {0, -1} for a clean member, and nothing else is launched or written for any member.  Then the plan of every member (keys, radix
+ * sort, run table: one set of launches per member, once per epoch), and for st = 0 .. max_r n_steps_r - 1 ONE launch of each kind
+ * for the whole group, the member being the grid's second dimension: the coefficient kernel; the Gamma rows kernel and the
+ * adversarial coefficient kernel when at least one member has adv_reg != 0; the gradient rows kernel; the Adam pass.  A workgroup
+ * leaves at once when st >= n_steps_r (the member's epoch is over: its tables, moments and zeroed gradient are not touched
+ * again), when it lies beyond the member's own grid for this step, or when the kernel is an adversarial one and the member has
+ * adv_reg == 0 (its areas of steps 2-4 stay unwritten).  The members' constants (pointers, sizes, hyperparameters, fl(lam / nb) of
+ * the full and of the short step) and the Adam coefficients of every (member, step), from the host function rk_apr_train_epoch
+ * uses, go to the device once per epoch; a step passes its index alone.  Every member runs the code path rk_apr_train_epoch would
+ * take for it (the float4 loads at dim == 64 by its own table's alignment).  No float atomics, no cooperative launch.
+ * RK_EINVAL with nothing launched and nothing written: n_rep outside 1..RK_APR_MAX_GROUP, a missing array or pointer, members
+ * whose dim differ, anything rk_apr_train_epoch refuses for any member, two members whose table, m, v, grad or workspace byte
+ * ranges overlap. */
+#define RK_APR_MAX_GROUP 64
+int rk_apr_train_epoch_group(int32_t n_rep, const rk_apr_desc *descs, const int64_t *const *users, const int64_t *const *pos,
+                             const int64_t *const *neg, const int64_t *n, int32_t batch, const int32_t *adam_t0,
+                             int32_t apply_update, double *const *losses, int32_t *status /*int32[2*n_rep]*/, void *stream);
 
 /* ---------------------------------------------------------------- Mult-VAE victim --------- */
 /* Mult-VAE (Liang, Krishnan, Hoffman and Jebara, WWW 2018, "Variational Autoencoders for Collaborative Filtering"): a

@@ -32,6 +32,7 @@ RK_EASE_BAD_GRAM, RK_EASE_NOT_SPD = 5, 6
 RK_IALS_MAX_DIM, RK_IALS_CHUNK, RK_IALS_GRAM_ROWS, RK_IALS_NOT_SPD = 128, 64, 256, 7
 RK_SLIM_MAX_ITEMS, RK_SLIM_BAD_DIAG = 20464, 8
 RK_APR_MAX_DIM, RK_APR_MAX_BATCH = 256, 65536
+RK_APR_MAX_GROUP = 64     # members of one rk_apr_train_epoch_group call
 RK_APR_RULES = {9: "a user id outside [0, n_users)", 10: "a positive item id outside [0, n_items)",
                 11: "a negative item id outside [0, n_items)"}
 
@@ -333,6 +334,9 @@ _SIGNATURES = {
     "rk_slim_fit": [_I32, _P, _F, _I32, _P, _P, _P, _P, _P],
     "rk_apr_workspace": [_I32, _I32, _I32, _I64, _I32, C.POINTER(AprLayout)],
     "rk_apr_train_epoch": [C.POINTER(AprDesc), _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],
+    # host arrays: descs [n_rep], users / pos / neg / losses (n_rep device pointers each), n (int64 [n_rep]), adam_t0 (int32 [n_rep])
+    "rk_apr_train_epoch_group": [_I32, C.POINTER(AprDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                 C.POINTER(C.c_int64), _I32, C.POINTER(C.c_int32), _I32, C.POINTER(C.c_void_p), _P, _P],
     "rk_mvae_workspace": [_I32, _I32, _I32, _I32, _I64, C.POINTER(MvaeLayout)],
     "rk_mvae_train_epoch": [C.POINTER(MvaeDesc), _P, _I64, _I32, _I64, _I32, _P, _P, _P],
     "rk_mvae_scores": [C.POINTER(MvaeDesc), _P, _I32, _P, _I64, _P],

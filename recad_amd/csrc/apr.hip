@@ -6,6 +6,8 @@
 // contribution rows are stored: a contribution is c_b times a row that is in the table anyway).
 #include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <vector>
 
 #include <hipcub/hipcub.hpp>
 
@@ -116,12 +118,13 @@ __device__ __forceinline__ double apr_group_sum(double v)
 // are the correctly rounded values of the fp32 rows but for the last bits of a 16-lane tree of doubles.  This costs a few fp64
 // operations per lane, and it matters: Adam divides by sqrt(v), and over the first steps of a training a last-bit error of c
 // is what moves the tables furthest from the float64 run.
+// The bodies take the step record and the workgroup's index in the step's own grid: rk_apr_train_epoch launches them one model at
+// a time, rk_apr_train_epoch_group with the member as the grid's second dimension.
 template <bool VEC4, bool ADV>
-__global__ __launch_bounds__(256) void apr_coef_kernel(AprStep a)
+__device__ __forceinline__ void apr_coef_body(const AprStep &a, const int block, double *red)
 {
-    __shared__ double red[4];
     const int g = threadIdx.x / kAprGroup, l = threadIdx.x % kAprGroup;
-    const int b = blockIdx.x * kAprTripletsPerBlock + g;
+    const int b = block * kAprTripletsPerBlock + g;
     double sp = 0.0, sq = 0.0;
     if (b < a.nb) {
         const int d = a.d;
@@ -171,11 +174,18 @@ __global__ __launch_bounds__(256) void apr_coef_kernel(AprStep a)
     }
     const double s = block_sum_256(sp, red);
     if (ADV) {
-        if (threadIdx.x == 0) a.part[2 * a.part_blocks + blockIdx.x] = s;
+        if (threadIdx.x == 0) a.part[2 * a.part_blocks + block] = s;
     } else {
         const double r = block_sum_256(sq, red);
-        if (threadIdx.x == 0) { a.part[blockIdx.x] = s; a.part[a.part_blocks + blockIdx.x] = r; }
+        if (threadIdx.x == 0) { a.part[block] = s; a.part[a.part_blocks + block] = r; }
     }
+}
+
+template <bool VEC4, bool ADV>
+__global__ __launch_bounds__(256) void apr_coef_kernel(AprStep a)
+{
+    __shared__ double red[4];
+    apr_coef_body<VEC4, ADV>(a, blockIdx.x, red);
 }
 
 // One wave per touched row (slot).  The run is walked 64 incidences at a time: lane i loads incidence i's (b, role, c_b) and
@@ -183,9 +193,9 @@ __global__ __launch_bounds__(256) void apr_coef_kernel(AprStep a)
 // elements k = lane + 64 j of the row in key order.
 // GRAD == 0: Gamma (step 2), its norm, Delta (step 3) and slot_of.  GRAD == 1: the row of step 5 into the dense gradient.
 template <bool GRAD, int REGS>
-__global__ __launch_bounds__(256) void apr_rows_kernel(AprStep a)
+__device__ __forceinline__ void apr_rows_body(const AprStep &a, const int block)
 {
-    const int lane = threadIdx.x & 63, slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, slot = block * 4 + (threadIdx.x >> 6);
     if (slot >= a.run[0]) return;
     const int beg = a.run[1 + slot], end = a.run[2 + slot], d = a.d;
     const int row = apr_key_row(a.keys[beg]);
@@ -275,15 +285,22 @@ __global__ __launch_bounds__(256) void apr_rows_kernel(AprStep a)
     }
 }
 
+template <bool GRAD, int REGS>
+__global__ __launch_bounds__(256) void apr_rows_kernel(AprStep a)
+{
+    apr_rows_body<GRAD, REGS>(a, blockIdx.x);
+}
+
 // The Adam pass over all N * d elements: reads g and stores 0 in its place, copies it out when asked, updates when asked.
 // Workgroup 0 also adds the step's loss partials in a fixed order: losses = {L, L', R}.
-__global__ __launch_bounds__(256) void apr_adam_kernel(long long n, float *p, float *g, float *m, float *v, float *grad_out, int apply_update,
-                                                       float step_size, float bc2s, float b1, float b2, float eps, const double *part,
-                                                       int part_blocks, int used_blocks, int nb, float lam, int adv, double *losses)
+// block of n_blocks: the workgroup's place in the pass over this model's elements
+__device__ __forceinline__ void apr_adam_body(long long n, float *p, float *g, float *m, float *v, float *grad_out, int apply_update,
+                                              float step_size, float bc2s, float b1, float b2, float eps, const double *part,
+                                              int part_blocks, int used_blocks, int nb, float lam, int adv, double *losses, const int block,
+                                              const int n_blocks, double *red)
 {
-    __shared__ double red[4];
     const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    for (long long i = (long long)block * blockDim.x + threadIdx.x; i < n; i += (long long)n_blocks * blockDim.x) {
         const float gi = g[i];
         g[i] = 0.f;
         if (grad_out) grad_out[i] = gi;
@@ -293,7 +310,7 @@ __global__ __launch_bounds__(256) void apr_adam_kernel(long long n, float *p, fl
             p[i] = pp; m[i] = mm; v[i] = vv;
         }
     }
-    if (blockIdx.x != 0) return;
+    if (block != 0) return;
     double s[3] = {0.0, 0.0, 0.0};
     for (int q = 0; q < 3; ++q) {
         if (q == 2 && !adv) break;
@@ -306,6 +323,15 @@ __global__ __launch_bounds__(256) void apr_adam_kernel(long long n, float *p, fl
         losses[1] = s[2] / (double)nb;
         losses[2] = (double)lam * 0.5 * s[1] / (double)nb;
     }
+}
+
+__global__ __launch_bounds__(256) void apr_adam_kernel(long long n, float *p, float *g, float *m, float *v, float *grad_out, int apply_update,
+                                                       float step_size, float bc2s, float b1, float b2, float eps, const double *part,
+                                                       int part_blocks, int used_blocks, int nb, float lam, int adv, double *losses)
+{
+    __shared__ double red[4];
+    apr_adam_body(n, p, g, m, v, grad_out, apply_update, step_size, bc2s, b1, b2, eps, part, part_blocks, used_blocks, nb, lam, adv, losses,
+                  blockIdx.x, gridDim.x, red);
 }
 
 // ---- host
@@ -372,24 +398,38 @@ RK_EXPORT int rk_apr_workspace(int32_t n_users, int32_t n_items, int32_t dim, in
     return RK_OK;
 }
 
+// what rk_apr_train_epoch refuses before it launches anything, and the layout of the epoch
+static int apr_check_args(const char *who, const rk_apr_desc &D, const int64_t *users, const int64_t *pos, const int64_t *neg, int64_t n,
+                          int32_t batch, int32_t adam_t0, int32_t apply_update, const double *losses, rk_apr_layout *L)
+{
+    if (!users || !pos || !neg || !losses) RK_FAIL(RK_EINVAL, "%s: a missing pointer", who);
+    if (!D.table || !D.m || !D.v || !D.workspace) RK_FAIL(RK_EINVAL, "%s: a missing pointer in the descriptor", who);
+    if (!apply_update && !D.grad) RK_FAIL(RK_EINVAL, "%s: apply_update = 0 needs desc.grad", who);
+    if (!(D.eps >= 0.f) || !std::isfinite(D.eps) || !(D.adv_reg >= 0.f) || !std::isfinite(D.adv_reg))
+        RK_FAIL(RK_EINVAL, "%s: eps and adv_reg must be finite and >= 0", who);
+    if (adam_t0 < 0) RK_FAIL(RK_EINVAL, "%s: adam_t0 < 0", who);
+    int rc = apr_limits(who, D.n_users, D.n_items, D.dim, n, batch);
+    if (rc) return rc;
+    rc = rk_apr_workspace(D.n_users, D.n_items, D.dim, n, batch, L);
+    if (rc) return rc;
+    if (D.workspace_bytes < L->bytes || (reinterpret_cast<uintptr_t>(D.workspace) & 255))
+        RK_FAIL(RK_EINVAL, "%s: the workspace has %lld bytes, %lld are needed (256-byte aligned)", who, (long long)D.workspace_bytes,
+                (long long)L->bytes);
+    return RK_OK;
+}
+
+static const char *const kAprRuleText[] = {"a user id outside [0, n_users)", "a positive item id outside [0, n_items)",
+                                           "a negative item id outside [0, n_items)"};
+static const char *apr_rule_text(int rule) { return kAprRuleText[rule >= RK_APR_BAD_USER && rule <= RK_APR_BAD_NEG ? rule - RK_APR_BAD_USER : 0]; }
+
 RK_EXPORT int rk_apr_train_epoch(const rk_apr_desc *desc, const int64_t *users, const int64_t *pos, const int64_t *neg, int64_t n,
                                  int32_t batch, int32_t adam_t0, int32_t apply_update, double *losses, int32_t *status, void *stream)
 {
-    if (!desc || !users || !pos || !neg || !losses || !status) RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: a missing pointer");
+    if (!desc || !status) RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: a missing pointer");
     const rk_apr_desc &D = *desc;
-    if (!D.table || !D.m || !D.v || !D.workspace) RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: a missing pointer in the descriptor");
-    if (!apply_update && !D.grad) RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: apply_update = 0 needs desc.grad");
-    if (!(D.eps >= 0.f) || !std::isfinite(D.eps) || !(D.adv_reg >= 0.f) || !std::isfinite(D.adv_reg))
-        RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: eps and adv_reg must be finite and >= 0");
-    if (adam_t0 < 0) RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: adam_t0 < 0");
     rk_apr_layout L;
-    int rc = apr_limits("rk_apr_train_epoch", D.n_users, D.n_items, D.dim, n, batch);
+    int rc = apr_check_args("rk_apr_train_epoch", D, users, pos, neg, n, batch, adam_t0, apply_update, losses, &L);
     if (rc) return rc;
-    rc = rk_apr_workspace(D.n_users, D.n_items, D.dim, n, batch, &L);
-    if (rc) return rc;
-    if (D.workspace_bytes < L.bytes || (reinterpret_cast<uintptr_t>(D.workspace) & 255))
-        RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: the workspace has %lld bytes, %lld are needed (256-byte aligned)", (long long)D.workspace_bytes,
-                (long long)L.bytes);
     hipStream_t s = (hipStream_t)stream;
     const int U = D.n_users, d = D.dim, n_steps = L.n_steps;
     const long long N = (long long)D.n_users + D.n_items;
@@ -408,10 +448,7 @@ RK_EXPORT int rk_apr_train_epoch(const rk_apr_desc *desc, const int64_t *users, 
         RK_HIP(hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, s));
         RK_HIP(hipStreamSynchronize(s));
         if (h[0]) {
-            static const char *const what[] = {"a user id outside [0, n_users)", "a positive item id outside [0, n_items)",
-                                               "a negative item id outside [0, n_items)"};
-            RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: rule %d (%s), first in triplet %d", h[0],
-                    what[h[0] >= RK_APR_BAD_USER && h[0] <= RK_APR_BAD_NEG ? h[0] - RK_APR_BAD_USER : 0], h[1]);
+            RK_FAIL(RK_EINVAL, "rk_apr_train_epoch: rule %d (%s), first in triplet %d", h[0], apr_rule_text(h[0]), h[1]);
         }
     }
 
@@ -469,6 +506,258 @@ RK_EXPORT int rk_apr_train_epoch(const rk_apr_desc *desc, const int64_t *users, 
         const AdamCoef co = adam_coef(adam_t0 + st + 1, D.lr, D.beta1, D.beta2);
         hipLaunchKernelGGL(apr_adam_kernel, dim3(adam_grid), dim3(256), 0, s, nd, D.table, gbuf, D.m, D.v, D.grad, apply_update, co.step_size,
                            co.bc2s, D.beta1, D.beta2, D.adam_eps, part, L.part_blocks, coef_grid, nb, D.lam, adv ? 1 : 0, losses + 3 * (size_t)st);
+        RK_CHECK_LAUNCH();
+    }
+    return RK_OK;
+}
+
+// ---- a group of models in shared launches (rk_apr_train_epoch_group)
+// What a member's steps have in common, written to the device once per epoch: `first` is the record of step 0 (a full step, or
+// the only one), a later step moves its triplets, keys and run table on, and the last one has its own nb and fl(lam / nb).
+struct AprMember {
+    AprStep first;
+    const AdamCoef *coef;                 // [n_steps]: adam_coef(adam_t0 + st + 1, ...) from the host
+    float *p, *m, *v, *grad_out;
+    double *losses;
+    long long n, nd;
+    int n_items, n_steps, batch, run_stride, nb_last, adam_grid, vec4, adv;
+    float lam_b_last, lam, b1, b2, adam_eps;
+};
+
+// the member's record of step st; false when its epoch is over
+__device__ __forceinline__ bool apr_member_step(const AprMember &M, const int st, AprStep &a)
+{
+    if (st >= M.n_steps) return false;
+    a = M.first;
+    const long long first = (long long)st * M.batch;
+    a.users += first; a.pos += first; a.neg += first;
+    a.keys += 3 * first;
+    a.run += (size_t)st * M.run_stride;
+    if (st == M.n_steps - 1) { a.nb = M.nb_last; a.lam_b = M.lam_b_last; }
+    return true;
+}
+
+__global__ void apr_group_check_kernel(const AprMember *__restrict__ members, unsigned long long *__restrict__ first_bad)
+{
+    const AprMember &M = members[blockIdx.y];
+    const int64_t *users = M.first.users, *pos = M.first.pos, *neg = M.first.neg;
+    const int U = M.first.U, I = M.n_items;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < M.n; t += (long long)gridDim.x * blockDim.x) {
+        const int64_t u = users[t], i = pos[t], j = neg[t];
+        int rule = 0;
+        if (u < 0 || u >= U) rule = RK_APR_BAD_USER;
+        else if (i < 0 || i >= I) rule = RK_APR_BAD_POS;
+        else if (j < 0 || j >= I) rule = RK_APR_BAD_NEG;
+        if (rule) atomicMin(first_bad + blockIdx.y, (unsigned long long)t * 16ULL + (unsigned long long)rule);
+    }
+}
+
+__global__ void apr_group_status_kernel(const unsigned long long *__restrict__ first_bad, int n_rep, int *__restrict__ status)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rep) return;
+    const unsigned long long k = first_bad[r];
+    const bool ok = k == ~0ULL;
+    status[2 * r] = ok ? 0 : (int)(k & 15ULL);
+    status[2 * r + 1] = ok ? -1 : (int)(k >> 4);
+}
+
+template <bool ADV>
+__global__ __launch_bounds__(256) void apr_group_coef_kernel(const AprMember *__restrict__ members, int st)
+{
+    __shared__ double red[4];
+    const AprMember &M = members[blockIdx.y];
+    if (ADV && !M.adv) return;
+    AprStep a;
+    if (!apr_member_step(M, st, a)) return;
+    if ((int)blockIdx.x * kAprTripletsPerBlock >= a.nb) return;
+    if (M.vec4) apr_coef_body<true, ADV>(a, blockIdx.x, red);
+    else apr_coef_body<false, ADV>(a, blockIdx.x, red);
+}
+
+template <bool GRAD, int REGS>
+__global__ __launch_bounds__(256) void apr_group_rows_kernel(const AprMember *__restrict__ members, int st)
+{
+    const AprMember &M = members[blockIdx.y];
+    if (!GRAD && !M.adv) return;
+    AprStep a;
+    if (!apr_member_step(M, st, a)) return;
+    if ((int)blockIdx.x * 4 >= 3 * a.nb) return;
+    apr_rows_body<GRAD, REGS>(a, blockIdx.x);
+}
+
+__global__ __launch_bounds__(256) void apr_group_adam_kernel(const AprMember *__restrict__ members, int st, int apply_update)
+{
+    __shared__ double red[4];
+    const AprMember &M = members[blockIdx.y];
+    if (st >= M.n_steps || (int)blockIdx.x >= M.adam_grid) return;
+    const int nb = st == M.n_steps - 1 ? M.nb_last : M.batch;
+    const AdamCoef co = M.coef[st];
+    apr_adam_body(M.nd, M.p, M.first.grad, M.m, M.v, M.grad_out, apply_update, co.step_size, co.bc2s, M.b1, M.b2,
+                  M.adam_eps, M.first.part, M.first.part_blocks, (nb + kAprTripletsPerBlock - 1) / kAprTripletsPerBlock, nb, M.lam, M.adv,
+                  M.losses + 3 * (size_t)st, blockIdx.x, M.adam_grid, red);
+}
+
+template <bool GRAD>
+static void apr_group_launch_rows(int regs, dim3 grid, hipStream_t s, const AprMember *members, int st)
+{
+    if (regs == 1) hipLaunchKernelGGL((apr_group_rows_kernel<GRAD, 1>), grid, dim3(256), 0, s, members, st);
+    else if (regs == 2) hipLaunchKernelGGL((apr_group_rows_kernel<GRAD, 2>), grid, dim3(256), 0, s, members, st);
+    else hipLaunchKernelGGL((apr_group_rows_kernel<GRAD, 4>), grid, dim3(256), 0, s, members, st);
+}
+
+static bool apr_ranges_meet(const void *a, int64_t a_bytes, const void *b, int64_t b_bytes)
+{
+    if (!a || !b) return false;
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
+}
+
+RK_EXPORT int rk_apr_train_epoch_group(int32_t n_rep, const rk_apr_desc *descs, const int64_t *const *users, const int64_t *const *pos,
+                                       const int64_t *const *neg, const int64_t *n, int32_t batch, const int32_t *adam_t0,
+                                       int32_t apply_update, double *const *losses, int32_t *status, void *stream)
+{
+    static const char *const who = "rk_apr_train_epoch_group";
+    if (n_rep < 1 || n_rep > RK_APR_MAX_GROUP) RK_FAIL(RK_EINVAL, "%s: n_rep = %d, expected 1..%d", who, n_rep, RK_APR_MAX_GROUP);
+    if (!descs || !users || !pos || !neg || !n || !adam_t0 || !losses || !status) RK_FAIL(RK_EINVAL, "%s: a missing array", who);
+    rk_apr_layout L[RK_APR_MAX_GROUP];
+    for (int r = 0; r < n_rep; ++r) {
+        if (descs[r].dim != descs[0].dim) RK_FAIL(RK_EINVAL, "%s: member %d has dim = %d, member 0 has %d", who, r, descs[r].dim, descs[0].dim);
+        const int rc = apr_check_args(who, descs[r], users[r], pos[r], neg[r], n[r], batch, adam_t0[r], apply_update, losses[r], &L[r]);
+        if (rc) {
+            char text[sizeof(rk_err_buf)];
+            snprintf(text, sizeof(text), "%s", rk_err_buf);
+            RK_FAIL(rc, "member %d: %s", r, text);
+        }
+    }
+    for (int r = 0; r < n_rep; ++r) {
+        const rk_apr_desc &A = descs[r];
+        const int64_t a_bytes = 4 * ((int64_t)A.n_users + A.n_items) * A.dim;
+        const void *pa[5] = {A.table, A.m, A.v, A.grad, A.workspace};
+        const int64_t na[5] = {a_bytes, a_bytes, a_bytes, a_bytes, L[r].bytes};
+        for (int q = 0; q < r; ++q) {
+            const rk_apr_desc &B = descs[q];
+            const int64_t b_bytes = 4 * ((int64_t)B.n_users + B.n_items) * B.dim;
+            const void *pb[5] = {B.table, B.m, B.v, B.grad, B.workspace};
+            const int64_t nbq[5] = {b_bytes, b_bytes, b_bytes, b_bytes, L[q].bytes};
+            for (int x = 0; x < 5; ++x)
+                for (int y = 0; y < 5; ++y)
+                    if (apr_ranges_meet(pa[x], na[x], pb[y], nbq[y]))
+                        RK_FAIL(RK_EINVAL, "%s: members %d and %d share bytes of their tables, moments, gradients or workspaces", who, q, r);
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int d = descs[0].dim;
+
+    // the members' table and the Adam coefficients of every (member, step), built on the host
+    std::vector<AprMember> mem((size_t)n_rep);
+    std::vector<AdamCoef> coef;
+    std::vector<size_t> coef_at((size_t)n_rep);
+    int max_steps = 0;
+    long long max_n = 0;
+    bool any_adv = false;
+    for (int r = 0; r < n_rep; ++r) {
+        const rk_apr_desc &D = descs[r];
+        const rk_apr_layout &l = L[r];
+        char *ws = static_cast<char *>(D.workspace);
+        const long long first_last = (long long)(l.n_steps - 1) * batch;
+        AprMember &M = mem[(size_t)r];
+        memset(&M, 0, sizeof(M));
+        AprStep &a = M.first;
+        a.table = D.table;
+        a.users = users[r]; a.pos = pos[r]; a.neg = neg[r];
+        a.keys = reinterpret_cast<unsigned long long *>(ws + l.keys);
+        a.run = reinterpret_cast<int *>(ws + l.run);
+        a.nb = (int)std::min<long long>(batch, n[r]); a.U = D.n_users; a.d = d;
+        a.eps = D.eps; a.adv_reg = D.adv_reg; a.lam_b = D.lam / (float)a.nb;
+        a.x = reinterpret_cast<float *>(ws + l.x); a.c = reinterpret_cast<float *>(ws + l.c);
+        a.x_adv = reinterpret_cast<float *>(ws + l.x_adv); a.c_adv = reinterpret_cast<float *>(ws + l.c_adv);
+        a.gamma = reinterpret_cast<float *>(ws + l.gamma); a.norm = reinterpret_cast<float *>(ws + l.norm);
+        a.delta = reinterpret_cast<float *>(ws + l.delta); a.grad = reinterpret_cast<float *>(ws + l.grad);
+        a.slot_of = reinterpret_cast<int *>(ws + l.slot_of);
+        a.part = reinterpret_cast<double *>(ws + l.part); a.part_blocks = l.part_blocks;
+        M.p = D.table; M.m = D.m; M.v = D.v; M.grad_out = D.grad;
+        M.losses = losses[r];
+        M.n = n[r];
+        M.nd = ((long long)D.n_users + D.n_items) * d;
+        M.n_items = D.n_items; M.n_steps = l.n_steps; M.batch = batch; M.run_stride = l.run_stride;
+        M.nb_last = (int)(n[r] - first_last);
+        M.adam_grid = (int)std::max<long long>(1, std::min<long long>((M.nd + 255) / 256, 2048));
+        M.vec4 = d == 64 && (reinterpret_cast<uintptr_t>(D.table) & 15) == 0;
+        M.adv = D.adv_reg != 0.f;
+        M.lam_b_last = D.lam / (float)M.nb_last;
+        M.lam = D.lam; M.b1 = D.beta1; M.b2 = D.beta2; M.adam_eps = D.adam_eps;
+        coef_at[(size_t)r] = coef.size();
+        for (int st = 0; st < l.n_steps; ++st) coef.push_back(adam_coef(adam_t0[r] + st + 1, D.lr, D.beta1, D.beta2));
+        max_steps = std::max(max_steps, (int)l.n_steps);
+        max_n = std::max<long long>(max_n, n[r]);
+        any_adv = any_adv || M.adv;
+    }
+
+    RkScratch scratch(s);
+    AprMember *d_mem = nullptr;
+    AdamCoef *d_coef = nullptr;
+    unsigned long long *first_bad = nullptr;
+    RK_HIP(scratch.get(&d_mem, (size_t)n_rep));
+    RK_HIP(scratch.get(&d_coef, coef.size()));
+    RK_HIP(scratch.get(&first_bad, (size_t)n_rep));
+    for (int r = 0; r < n_rep; ++r) mem[(size_t)r].coef = d_coef + coef_at[(size_t)r];
+    // the two uploads are over when the synchronisation below returns, so the host copies may go when this function does
+    RK_HIP(hipMemcpyAsync(d_mem, mem.data(), sizeof(AprMember) * (size_t)n_rep, hipMemcpyHostToDevice, s));
+    RK_HIP(hipMemcpyAsync(d_coef, coef.data(), sizeof(AdamCoef) * coef.size(), hipMemcpyHostToDevice, s));
+
+    {   // the ids of all members first: nothing else is launched on a bad one
+        RK_HIP(hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long) * (size_t)n_rep, s));
+        hipLaunchKernelGGL(apr_group_check_kernel, dim3((int)std::min<long long>((max_n + 255) / 256, 4096), n_rep), dim3(256), 0, s, d_mem, first_bad);
+        RK_CHECK_LAUNCH();
+        hipLaunchKernelGGL(apr_group_status_kernel, dim3(1), dim3(RK_APR_MAX_GROUP), 0, s, first_bad, (int)n_rep, status);
+        RK_CHECK_LAUNCH();
+        int32_t h[2 * RK_APR_MAX_GROUP];
+        RK_HIP(hipMemcpyAsync(h, status, sizeof(int32_t) * 2 * (size_t)n_rep, hipMemcpyDeviceToHost, s));
+        RK_HIP(hipStreamSynchronize(s));
+        for (int r = 0; r < n_rep; ++r)
+            if (h[2 * r])
+                RK_FAIL(RK_EINVAL, "%s: member %d: rule %d (%s), first in triplet %d", who, r, h[2 * r], apr_rule_text(h[2 * r]), h[2 * r + 1]);
+    }
+
+    // every member's plan, once per epoch
+    for (int r = 0; r < n_rep; ++r) {
+        const rk_apr_desc &D = descs[r];
+        const rk_apr_layout &l = L[r];
+        char *ws = static_cast<char *>(D.workspace);
+        unsigned long long *keys = reinterpret_cast<unsigned long long *>(ws + l.keys), *keys_in = reinterpret_cast<unsigned long long *>(ws + l.keys_in);
+        hipLaunchKernelGGL(apr_keys_kernel, dim3((int)std::min<long long>((n[r] + 255) / 256, 4096)), dim3(256), 0, s, users[r], pos[r], neg[r],
+                           (long long)n[r], batch, D.n_users, keys_in);
+        RK_CHECK_LAUNCH();
+        size_t sort_bytes = (size_t)l.sort_tmp_bytes;
+        RK_HIP(hipcub::DeviceRadixSort::SortKeys(ws + l.sort_tmp, sort_bytes, (const unsigned long long *)keys_in, keys, (long long)(3 * n[r]), 0,
+                                                 apr_sort_bits(l.n_steps), s));
+        hipLaunchKernelGGL(apr_runs_kernel, dim3(l.n_steps), dim3(256), 0, s, keys, (long long)n[r], batch, l.run_stride, reinterpret_cast<int *>(ws + l.run));
+        RK_CHECK_LAUNCH();
+        RK_HIP(rk_zero_async(ws + l.grad, sizeof(float) * (size_t)mem[(size_t)r].nd, s));
+    }
+
+    const int regs = (d + kWave - 1) / kWave;
+    for (int st = 0; st < max_steps; ++st) {
+        int nb_max = 0, adam_max = 0;          // the widest grids among the members that still have a step st
+        for (int r = 0; r < n_rep; ++r) {
+            const AprMember &M = mem[(size_t)r];
+            if (st >= M.n_steps) continue;
+            nb_max = std::max(nb_max, st == M.n_steps - 1 ? M.nb_last : batch);
+            adam_max = std::max(adam_max, M.adam_grid);
+        }
+        const dim3 coef_grid((nb_max + kAprTripletsPerBlock - 1) / kAprTripletsPerBlock, n_rep), row_grid((3 * nb_max + 3) / 4, n_rep);
+        hipLaunchKernelGGL((apr_group_coef_kernel<false>), coef_grid, dim3(256), 0, s, d_mem, st);
+        RK_CHECK_LAUNCH();
+        if (any_adv) {
+            apr_group_launch_rows<false>(regs, row_grid, s, d_mem, st);
+            RK_CHECK_LAUNCH();
+            hipLaunchKernelGGL((apr_group_coef_kernel<true>), coef_grid, dim3(256), 0, s, d_mem, st);
+            RK_CHECK_LAUNCH();
+        }
+        apr_group_launch_rows<true>(regs, row_grid, s, d_mem, st);
+        RK_CHECK_LAUNCH();
+        hipLaunchKernelGGL(apr_group_adam_kernel, dim3(adam_max, n_rep), dim3(256), 0, s, d_mem, st, (int)apply_update);
         RK_CHECK_LAUNCH();
     }
     return RK_OK;

@@ -125,6 +125,13 @@ WORKFLOW = {
         "logging_level": logging.INFO, "device": DEVICE, "cache_dir": os.path.join(".", "workflows_results"),
         "quality_split": None,        # build-specific: None | "valid" | "test" = also report held-out Recall / NDCG / ... @k
     },
+    # build-specific: one clean victim, one poisoned retrain per case {"attacker", "target_id_list"} (workflow.Sweep)
+    "sweep": {
+        "rec_epoch": 400, "attack_epoch": 100, "filter_num": 4, "topks": [10, 20, 50, 100],
+        "logging_level": logging.INFO, "device": DEVICE, "cache_dir": os.path.join(".", "workflows_results"),
+        "quality_split": None,
+        "group": 8,                   # poisoned victims retrained per train_group call (victims that have one); 1 = one after another
+    },
 }
 
 

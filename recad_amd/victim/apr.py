@@ -21,7 +21,11 @@ is 200 because the workflows' default rec_epoch is 400 and the paper starts from
 run of tests/_apr_restate.py on the tiny set the data loss stayed at 0.693 for 40 epochs and recall@10 was 0.04 against 0.23).
 
 Optimizers: torch.optim.Adam with its default options runs fused in the library, its moments being the entries of
-``optimizer.state``; any other optimizer gets the dense gradient of each minibatch from the library and steps in torch."""
+``optimizer.state``; any other optimizer gets the dense gradient of each minibatch from the library and steps in torch.
+
+Groups: ``APR.train_group(victims, epochs)`` trains up to RK_APR_MAX_GROUP victims (fused Adam only) through
+rk_apr_train_epoch_group, one launch chain for all of them, each on its own dataset's triplets; every victim ends with the bits its
+own ``train_step`` loop would have given it.  ``workflow.Sweep`` retrains its poisoned victims that way."""
 import ctypes as C
 import math
 
@@ -126,6 +130,20 @@ class APR(BaseVictim):
         return self._ws
 
     # ------------------------------------------------------------------ training
+    def _desc(self, n, batch, adv_reg, apply_update, dev):
+        """rk_apr_desc of an epoch of n triplets in steps of `batch`: the tables, the moments, the workspace and the optimizer's options"""
+        m, v = self._moments(dev)
+        if not apply_update and (self._grad is None or self._grad.device != dev):
+            self._grad = torch.zeros_like(self.weight.data)
+        grp = self.optimizer.param_groups[0]
+        b1, b2 = grp.get("betas", (0.9, 0.999))
+        ws = self._workspace(n, batch, dev)
+        return _lib.AprDesc(
+            n_users=self.num_users, n_items=self.num_items, dim=self.dim, table=self.weight.data.data_ptr(), m=m.data_ptr(),
+            v=v.data_ptr(), grad=None if apply_update else self._grad.data_ptr(), lam=self.reg_lambda, eps=self.eps, adv_reg=adv_reg,
+            lr=float(grp.get("lr", 1e-3)), beta1=float(b1), beta2=float(b2), adam_eps=float(grp.get("eps", 1e-8)),
+            workspace=ws.data_ptr(), workspace_bytes=ws.numel())
+
     def _run_epoch(self, users, pos, neg, batch, adv_reg, apply_update=True):
         """ceil(n / batch) steps in the library -> double [n_steps, 3] = {L, L', R} per step, on the device."""
         check_config(self.dim, self.reg_lambda, self.eps, adv_reg, self.adv_start_epoch, batch=batch)
@@ -136,17 +154,7 @@ class APR(BaseVictim):
         n = users.numel()
         if n < 1:
             raise ValueError("APR: an epoch without triplets")
-        m, v = self._moments(dev)
-        if not apply_update and (self._grad is None or self._grad.device != dev):
-            self._grad = torch.zeros_like(self.weight.data)
-        grp = self.optimizer.param_groups[0]
-        b1, b2 = grp.get("betas", (0.9, 0.999))
-        ws = self._workspace(n, batch, dev)
-        desc = _lib.AprDesc(
-            n_users=self.num_users, n_items=self.num_items, dim=self.dim, table=self.weight.data.data_ptr(), m=m.data_ptr(),
-            v=v.data_ptr(), grad=None if apply_update else self._grad.data_ptr(), lam=self.reg_lambda, eps=self.eps, adv_reg=adv_reg,
-            lr=float(grp.get("lr", 1e-3)), beta1=float(b1), beta2=float(b2), adam_eps=float(grp.get("eps", 1e-8)),
-            workspace=ws.data_ptr(), workspace_bytes=ws.numel())
+        desc = self._desc(n, batch, adv_reg, apply_update, dev)
         n_steps = (n + batch - 1) // batch
         losses = torch.empty(3 * n_steps, dtype=torch.float64, device=dev)
         status = torch.zeros(2, dtype=torch.int32, device=dev)
@@ -193,13 +201,106 @@ class APR(BaseVictim):
 
             self._unfused_epoch((users, pos, neg), batch, grad_step)
             per_step = torch.stack(rows)
-        self.epochs_done += 1
-        mean = per_step.mean(dim=0)
-        self.last_losses = {"bpr": float(mean[0]), "adv": float(mean[1]), "reg": float(mean[2])}
-        loss = self.last_losses["bpr"] + adv_reg * self.last_losses["adv"] + self.last_losses["reg"]
+        loss = self._finish_epoch(per_step, adv_reg)
         if pbar:
             pbar.set_description(f"loss: {loss:.4f}")
         return (loss,)
+
+    def _finish_epoch(self, per_step, adv_reg):
+        """what an epoch leaves on the host side: the epoch count, last_losses -> the epoch's loss"""
+        self.epochs_done += 1
+        mean = per_step.mean(dim=0)
+        self.last_losses = {"bpr": float(mean[0]), "adv": float(mean[1]), "reg": float(mean[2])}
+        return self.last_losses["bpr"] + adv_reg * self.last_losses["adv"] + self.last_losses["reg"]
+
+    @staticmethod
+    def check_group(victims):
+        """The host-side refusals of train_group (ValueError), before any device call."""
+        victims = list(victims)
+        if not victims:
+            raise ValueError("APR.train_group: an empty group")
+        if len(victims) > _lib.RK_APR_MAX_GROUP:
+            raise ValueError(f"APR.train_group: {len(victims)} victims, at most {_lib.RK_APR_MAX_GROUP} train in one group (chunk the list)")
+        for r, v in enumerate(victims):
+            if not isinstance(v, APR) or not v.__dict__.get("_is_instantiate", False):
+                raise ValueError(f"APR.train_group: member {r} is {type(v).__name__}, expected an instantiated APR")
+            if any(v is w for w in victims[:r]):
+                raise ValueError(f"APR.train_group: member {r} is in the group twice")
+            if not v._fused_adam:
+                raise ValueError(f"APR.train_group: member {r} has the optimizer {type(v.optimizer).__name__}; a group trains under the fused "
+                                 "Adam only (train it with train_step)")
+        first = victims[0]
+        for r, v in enumerate(victims):
+            if v.dim != first.dim:
+                raise ValueError(f"APR.train_group: member {r} has factor_num = {v.dim}, member 0 has {first.dim}")
+            if v.weight.device != first.weight.device:
+                raise ValueError(f"APR.train_group: member {r} is on the device {v.weight.device}, member 0 on {first.weight.device}")
+        # the batch size a dataset of this build declares; a foreign dataset's is known once its epoch is drawn (train_group compares again)
+        configs = [getattr(v.dataset, "config", None) for v in victims]
+        APR._same_batch([c.get("pairwise_batch_size") if isinstance(c, dict) else None for c in configs])
+        return victims
+
+    @staticmethod
+    def _same_batch(sizes):
+        known = [(r, b) for r, b in enumerate(sizes) if b is not None]
+        for r, b in known:
+            if b != known[0][1]:
+                raise ValueError(f"APR.train_group: member {r} trains in minibatches of {b}, member {known[0][0]} in minibatches of {known[0][1]}")
+
+    @staticmethod
+    def train_group(victims, epochs=1, progress_bar=None):
+        """`epochs` epochs of every victim, each on the triplets of its own dataset, one rk_apr_train_epoch_group call per epoch
+        -> [[loss of epoch e for victim r]].  Every victim ends as `epochs` calls of its own train_step() would leave it, to the bit:
+        weight, moments, step counter, epochs_done, last_losses, and its dataset's sampler."""
+        victims = APR.check_group(victims)
+        if not (_count(epochs) and epochs >= 0):
+            raise ValueError(f"APR.train_group: epochs = {epochs!r}, expected an integer >= 0")
+        R, out = len(victims), []
+        for _ in range(epochs):
+            adv, cols, sizes = [], [], []
+            for v in victims:
+                v.train()
+                check_config(v.dim, v.reg_lambda, v.eps, v.adv_reg, v.adv_start_epoch)
+                adv.append(v._adv_reg_now())
+                c, batch = v._collect_epoch(v.dataset, ("users", "positive_items", "negative_items"))
+                check_config(v.dim, v.reg_lambda, v.eps, adv[-1], v.adv_start_epoch, batch=batch)
+                cols.append(c)
+                sizes.append(batch)
+            APR._same_batch(sizes)
+            batch = sizes[0]
+            dev = victims[0]._device()
+            _lib.require_gpu()
+            descs, ids, losses, ns = (_lib.AprDesc * R)(), [], [], []
+            for r, v in enumerate(victims):
+                if v._device() != dev:
+                    raise ValueError(f"APR.train_group: member {r} is on the device {v.weight.device}, member 0 on {dev}")
+                ids.append([t.to(dev).long().contiguous() for t in cols[r]])
+                n = ids[r][0].numel()
+                if n < 1:
+                    raise ValueError(f"APR.train_group: member {r} has an epoch without triplets")
+                descs[r] = v._desc(n, batch, adv[r], True, dev)
+                ns.append(n)
+                losses.append(torch.empty(3 * ((n + batch - 1) // batch), dtype=torch.float64, device=dev))
+            status = torch.zeros(2 * R, dtype=torch.int32, device=dev)
+            arr = lambda ts: (C.c_void_p * R)(*[t.data_ptr() for t in ts])
+            rc = _lib.lib().rk_apr_train_epoch_group(
+                R, descs, arr([i[0] for i in ids]), arr([i[1] for i in ids]), arr([i[2] for i in ids]), (C.c_int64 * R)(*ns), batch,
+                (C.c_int32 * R)(*[v._steps_done() for v in victims]), 1, arr(losses), _lib.ptr(status), _lib.stream_ptr(dev))
+            if rc != 0:
+                for r, (rule, t) in enumerate(status.cpu().view(R, 2).tolist()):
+                    if rule:
+                        raise ValueError(f"APR.train_group: the triplets of member {r} break rule {rule} ({_lib.RK_APR_RULES.get(rule, '?')}), "
+                                         f"first in triplet {t}")
+                _lib.check(rc, "rk_apr_train_epoch_group")
+            row = []
+            for r, v in enumerate(victims):
+                n_steps = losses[r].numel() // 3
+                v.optimizer.state[v.weight]["step"] += n_steps
+                row.append((v._finish_epoch(losses[r].view(n_steps, 3).cpu(), adv[r]),))
+            if progress_bar:
+                progress_bar.set_description("loss: " + " ".join(f"{x[0]:.4f}" for x in row))
+            out.append([x[0] for x in row])
+        return out
 
     # ------------------------------------------------------------------ scoring
     def _tables(self):

@@ -292,7 +292,94 @@ class Defense(Normal):
         return results
 
 
-factories = {"no defense": Normal, "defense": Defense}
+class Sweep(Normal):
+    """Perturb-and-retrain over many cases: ONE clean victim, then per case {"attacker": obj, "target_id_list": [...]} the steps of
+    Normal.execute (the attacker's own training, generate_fake, inject_data, a fresh victim on the poisoned set), the poisoned
+    victims retrained `group` at a time through the victim class's ``train_group`` (victim/apr.py: one launch chain for the whole
+    group, every member to the bit what its own train_step loop gives) -- one after another with normal_train when the class has
+    none or group is 1 -- and each evaluated against the one clean model.  execute() returns the result dictionaries in case order."""
+
+    def __init__(self, **config):
+        self.c = config
+        cases = list(config["cases"])
+        if not cases:
+            raise ValueError("sweep: no cases")
+        self.cases = []
+        for k, case in enumerate(cases):
+            if not isinstance(case, dict) or "attacker" not in case or not list(case.get("target_id_list", ())):
+                raise ValueError(f"sweep: case {k} must be a dict with 'attacker' and a non-empty 'target_id_list'")
+            self.cases.append({"attacker": case["attacker"].I(dataset=config["attack_data"]), "target_id_list": list(case["target_id_list"])})
+        group = config["group"]
+        if isinstance(group, bool) or not isinstance(group, int) or group < 1:
+            raise ValueError(f"sweep: group = {group!r}, expected an integer >= 1")
+        self.victim = config["victim"].I(dataset=config["victim_data"])
+        self.victim_data = config["victim_data"]
+        if config.get("quality_split") not in (None, "valid", "test"):
+            raise ValueError(f"quality_split must be None, 'valid' or 'test', got {config['quality_split']!r}")
+        self.logger = get_logger(__name__, level=config["logging_level"])
+        self.timings = OrderedDict()
+        self._targets = self.cases[0]["target_id_list"]
+
+    @classmethod
+    def from_config(cls, **kwargs):
+        need = ("victim_data", "attack_data", "victim", "cases")
+        if any(k not in kwargs for k in need):
+            raise TypeError(f"Expect for user arguments [{', '.join(need)}]")
+        config = {k: copy(v) for k, v in WORKFLOW["sweep"].items()}
+        for k, v in kwargs.items():
+            if k in config or k in need:
+                config[k] = v
+        return cls(**config)
+
+    def info_describe(self):
+        return {"target_id_list": self._targets, "input_describe": {}}
+
+    def train_poisoned(self, victims, epoch):
+        """-> per victim the list of train_step outputs, as normal_train returns it; `group` victims per train_group call"""
+        group, grouped = self.c["group"], getattr(type(self.victim), "train_group", None)
+        losses, self.timings["train_poisoned_s"] = [], []
+        for lo in range(0, len(victims), group):
+            chunk = victims[lo:lo + group]
+            t0 = time.time()
+            if group > 1 and grouped is not None:
+                per_epoch = grouped(chunk, epochs=epoch, progress_bar=NullProgress())
+                losses += [[(row[r],) for row in per_epoch] for r in range(len(chunk))]
+            else:
+                losses += [self.normal_train(v, epoch) for v in chunk]
+            self.timings["train_poisoned_s"].append(time.time() - t0)
+        return losses
+
+    def execute(self):
+        dev = self.c["device"]
+        tick = time.time
+        self.victim = self.victim.to(dev)
+        t0 = tick()
+        self.losses = self.normal_train(self.victim, self.c["rec_epoch"])
+        self.timings["train_clean_s"] = tick() - t0
+        self.fake_datasets, self.fake_victims = [], []
+        for case in self.cases:
+            self._targets = case["target_id_list"]
+            attacker = case["attacker"] = case["attacker"].to(dev)
+            if "train_step" in attacker.input_describe():
+                self.normal_train(attacker, self.c["attack_epoch"])
+            fake_array = attacker.generate_fake(**self.info_describe())
+            fake_dataset = self.victim_data.inject_data("explicit", fake_array, filter_num=self.c["filter_num"])
+            self.fake_datasets.append(fake_dataset)
+            self.fake_victims.append(self.victim.reset().I(dataset=fake_dataset).to(dev))
+        self.losses_fake = self.train_poisoned(self.fake_victims, self.c["rec_epoch"])
+        t0 = tick()
+        split, topks = self.c.get("quality_split"), self.c["topks"]
+        # the clean model is evaluated once per case: its held-out quality is computed once and handed to every evaluation
+        clean_q = None
+        if split is not None and self._batched(self.victim):
+            clean_q = heldout_quality(self.victim, self.victim_data, split=split, topks=topks)
+        self.results = [self.normal_evaluate(self.victim, fake, self.victim_data, case["target_id_list"], topks, quality_clean=clean_q)
+                        for case, fake in zip(self.cases, self.fake_victims)]
+        self.timings["evaluate_s"] = tick() - t0
+        return self.results
+
+
+factories = {"no defense": Normal, "defense": Defense, "sweep": Sweep}
 
 
 def from_config(name, **kwargs):
