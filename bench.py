@@ -11,6 +11,18 @@ the pre-sampled triplets already resident in HBM, after W untimed steps on the S
 captured hipGraph (victim.reserve(): nothing is allocated, captured or instantiated inside the timed
 region).  The full-catalog scoring + top-100 + HR@K pass is timed after it ("topk").
 
+A plain run does what that line needs and no more: set-up, the lead-in of the timed call (the dominant-kernel
+probe that brings the device to its working clocks -- its `roofline` figure comes with it -- and the W warm-up
+steps), the K timed steps, the metric's evaluation leg on the tables the run leaves (the diagnostic repeat of
+the call and the two `train_step()` epochs in front of it train those tables further, so they stay: the
+evaluation's top-K lists are part of what --dump-outputs writes), the outputs, the line.  `--full` adds
+everything else the benchmark measures or checks, each in its own key of the same line and each with its own
+`--no-...` switch: the live rocprofv3 counter passes behind `roofline.traffic`, the oracle replay (`parity`,
+`cpu_baseline_port`), the ATen CPU baseline (`cpu_baseline`), the yelp- and config-4-shaped measurements
+(`also`), the d = 256 scoring GEMM (`mfma_gemm`), the evaluation session's comparison with the plain call and
+the single-evaluation latency (`topk.single_evaluation_seconds`), and for N > 1 the sharded legs of `also`.
+Without `--full` those keys are null.
+
 N > 1: `python bench.py --gpus N` starts its own N worker processes (one per GPU, before anything touches a
 GPU); under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it is a worker itself.
 The TOP-LEVEL line is the SAME quantity for every N: the metric's own workload (ml1m-shaped, the one `--gpus 1`
@@ -47,6 +59,10 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: one ml1m epoch = 458; 20 for the larger shapes / sharded modes)")
     ap.add_argument("--warmup", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the live counter passes of the roofline, the oracle replay (parity, cpu_baseline_port), the ATen "
+                         "CPU baseline, the yelp- and config-4-shaped measurements (`also`), the d = 256 scoring GEMM, the evaluation session's "
+                         "comparison with the plain call, the N > 1 sharded legs -- each of them has its own --no-... switch; without --full none runs")
     ap.add_argument("--workload", default=None, choices=["ml1m", "yelp", "tiny", "c4s", "config4"],
                     help="default: ml1m (BASELINE.json config[1]) for every N")
     ap.add_argument("--graph", default="train", choices=["train", "reference"],
@@ -60,8 +76,8 @@ def parse(argv=None):
                          "csr (row gather) -- A/B of the two forms on one graph")
     ap.add_argument("--no-block-list", action="store_true", help="row-gather path: start every workgroup in the row-filtered last forward layer (A/B of the marked-block list)")
     ap.add_argument("--fuse-layers", action="store_true", help="LDS path: the L layers of a pass as one multi-phase launch (opt-in form, measured slower)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the oracle replay of the timed path (parity object, cpu_baseline_port)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the ATen CPU baseline (cpu_baseline)")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the oracle replay of the timed path (parity object, cpu_baseline_port)")
     ap.add_argument("--parity-steps", type=int, default=0, help="oracle steps laid next to the timed run (0 = 25 at ml1m size, 3 at yelp size)")
     ap.add_argument("--no-topk", action="store_true", help="skip the evaluation leg")
     ap.add_argument("--deterministic", action="store_true",
@@ -86,16 +102,16 @@ def parse(argv=None):
                     help="labelled extra mode (SURVEY 8d config 3): time train(clean) + inject 50 fake users + train(poisoned) + 2 x "
                          "evaluation through workflow.execute(), with the graph / schedule rebuild of the retrain loop itemised")
     ap.add_argument("--rec-epoch", type=int, default=2, help="--workflow: training epochs per (re)train")
-    ap.add_argument("--no-also", action="store_true", help="N = 1 default run: skip the short yelp-shaped measurement (`also`)")
+    ap.add_argument("--no-also", action="store_true", help="--full, N = 1 on the default workload: skip the short yelp-shaped measurement (`also`)")
     ap.add_argument("--no-also-config4", action="store_true",
-                    help="N = 1 default run: skip the config-4-shaped measurement (1M x 500K x 100M edges, ~6 s) inside `also`")
+                    help="--full, N = 1 on the default workload: skip the config-4-shaped measurement (1M x 500K x 100M edges, ~6 s) inside `also`")
     ap.add_argument("--no-also-sharded", action="store_true",
-                    help="N > 1 default run: skip the strong-scaling legs (ONE job sharded over the N GPUs: config-4 and yelp shapes, rows2d) in `also`")
+                    help="--full, N > 1: skip the strong-scaling legs (ONE job sharded over the N GPUs: config-4 and yelp shapes, rows2d) in `also`")
     ap.add_argument("--also-timeout", type=float, default=480.0,
                     help="N > 1: seconds the sharded `also` legs may take before the (already measured) top-level line is printed without them")
     ap.add_argument("--share-gpu", action="store_true", help="box check: several nccl / gloo ranks on ONE GPU (rank -> device rank %% n_devices)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="N = 1: do not run the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic in this run")
+                    help="--full, N = 1: do not run the two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) that measure roofline.traffic in this run")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: workers rendezvous over gloo, all-reduce their ranks and exit")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -103,6 +119,8 @@ def parse(argv=None):
                          "64 MB in all; larger outputs as a fixed seeded row sample + <name>_rows.npy): the per-step losses of the timed "
                          "steps and the embedding tables after the last one, and the last timed evaluation's top-K lists and target ranks")
     a = ap.parse_args(argv)
+    if not a.full:   # a plain run: the headline figure alone, every leg that --full adds is off
+        a.no_cpu_baseline = a.no_parity = a.no_also = a.no_also_sharded = a.no_live_traffic = True
     if a.workload is None:
         a.workload = "ml1m"          # the metric's own workload for EVERY N: the 1 -> 8 series is one quantity
     if a.parallel is None:
@@ -174,7 +192,7 @@ def dry_run_worker(args, rank, world):
     dist.barrier()
     if rank == 0:
         out = {"dry_run": True, "n_gpus": world, "rank_sum": float(t.item()), "parallel": args.parallel, "workload": args.workload,
-               "metric": metric_for(args), "steps": args.steps, "warmup": args.warmup,
+               "metric": metric_for(args), "steps": args.steps, "warmup": args.warmup, "full": bool(args.full),
                "scaling": "strong" if (args.parallel in ("rows", "rows2d") and (world > 1 or args.force_collectives)) else "weak",
                "also_sharded_legs": (also_sharded_leg_names(args.no_also_config4) if (world > 1 and args.parallel == "replicas" and not args.no_also_sharded) else [])}
         if args.workload not in ("c4s", "config4"):
@@ -473,6 +491,15 @@ def ranks_seen(dev, world, collectives):
     dist.all_gather(out, t)
     return {"world_size": int(dist.get_world_size()), "backend": dist.get_backend(),
             "devices": [{"rank": int(o[0]), "device_index": int(o[1]), "pci_bus_id": int(o[2])} for o in out], "name": props.name}
+
+
+def check_session_against_plain_call(victim, users, ptr, idx, targets, chunk, got):
+    """--full: what an EvalSession run returned (`got`) against the plain full_catalog_topk call on the same victim."""
+    import torch
+    from recad_amd.evaluate import full_catalog_topk, hit_counts
+    ref = full_catalog_topk(victim, users, ptr, idx, targets, K=100, chunk=chunk, to_host=False)
+    assert torch.equal(ref["top_ids"], got["top_ids"]) and torch.equal(ref["target_rank"], got["target_rank"]), "EvalSession != full_catalog_topk"
+    assert torch.equal(hit_counts(ref["target_rank"], (10, 20, 50, 100)), got["hit_counts"])
 
 
 def wait_done(stream):
@@ -959,7 +986,11 @@ def worker(args, traffic_live=None):
     N, nnz = g.n_rows, g.nnz
     users, pos, neg = resident_triplets(ds, (args.steps + args.warmup) * B)
     host_triplets = tuple(t[: B * 64].cpu().numpy() for t in (users, pos, neg))  # cpu_baseline / parity sample
-    want_parity = world == 1 and not collectives and not big and not args.no_parity
+    parity_shape = world == 1 and not collectives and not big
+    want_parity = parity_shape and not args.no_parity
+    # a plain run keeps in front of its timed call what a --full run has there (the device-side copy of the warm-up's losses sits
+    # between the warm-up and the opening barrier): the two modes time the same call behind the same lead-in
+    keep_warm_losses = want_parity or (parity_shape and not args.full)
     n_par = min(args.warmup + args.steps, args.parity_steps or (25 if args.workload in ("ml1m", "tiny") else 3), 64) if want_parity else 0
     init_tables = tuple(p_.detach().cpu().numpy().copy() for p_ in (victim.embedding_user.weight, victim.embedding_item.weight)) if want_parity else None
     victim.reserve(max(args.steps, args.warmup) * B, B)   # staging + hipGraph capture/upload, before any timing
@@ -980,14 +1011,14 @@ def worker(args, traffic_live=None):
     #     ~4x slower (25 us instead of 6 for the handle check alone: 150 us of a 1.4 ms region with the device waiting);
     # (3) nothing else: the reduction that copies the warm-up's losses is run once on a dummy BEFORE (1), so its code object
     #     is loaded by then (loading it between warm-up and timed call left the device idle for milliseconds).
-    if want_parity and args.warmup > 0:
+    if keep_warm_losses and args.warmup > 0:
         torch.zeros(args.warmup, _lib.RK_LOSS_PARTIALS, device=dev).sum(dim=1).double()
         torch.cuda.synchronize()
     roofline = spmm_roofline(args, victim, N, nnz, traffic_live)
     warm_losses = None
     if args.warmup > 0:
         wp = run_steps(victim, (users, pos, neg), B, 0, args.warmup)
-        if want_parity:
+        if keep_warm_losses:
             warm_losses = wp.sum(dim=1).double()   # device-side copy now (the loss buffer is reused by the timed call), read back after the timing
     ev_a, ev_b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     timed_cols = tuple(t[args.warmup * B: (args.warmup + args.steps) * B] for t in (users, pos, neg))   # (views of the resident triplets)
@@ -1080,10 +1111,8 @@ def worker(args, traffic_live=None):
         for _ in range(3):   # eager, capture + replay, replay
             warm = sess.run()
         int(warm["hit_counts"][0, 2].item())
-        ref = full_catalog_topk(victim, ev_dev, ptr_dev, idx_dev, tg_dev, K=100, chunk=ev_chunk, to_host=False)   # the session against the plain call
-        assert torch.equal(ref["top_ids"], warm["top_ids"]) and torch.equal(ref["target_rank"], warm["target_rank"]), "EvalSession != full_catalog_topk"
-        assert torch.equal(hit_counts(ref["target_rank"], (10, 20, 50, 100)), warm["hit_counts"])
-        del ref
+        if args.full:
+            check_session_against_plain_call(victim, ev_dev, ptr_dev, idx_dev, tg_dev, ev_chunk, warm)
         # EV_REPS complete evaluations back to back, one sync at the end
         EV_REPS = 8 if nnz < 20_000_000 else 2
         for _ in range(4 if nnz < 20_000_000 else 1):   # (the comparison above left the device idle: replays in front of the timed ones, as a
@@ -1102,10 +1131,12 @@ def worker(args, traffic_live=None):
         if args.dump_outputs and rank == 0:   # the last timed evaluation, read back now (the next session run overwrites its buffers;
             dump["eval_users"] = np.asarray(ev_users)   # a synchronous copy, so nothing of it is queued into the latency measured below)
             dump.update({k: res[k].cpu().numpy() for k in ("top_ids", "top_scores", "target_score", "target_rank", "hit_counts")})
-        t1 = time.perf_counter()  # one evaluation on an idle device through the plain call, host enqueue included (latency, not throughput)
-        res = full_catalog_topk(victim, ev_dev, ptr_dev, idx_dev, tg_dev, K=100, chunk=ev_chunk, to_host=False)
-        hit_counts(res["target_rank"], (10, 20, 50, 100)).cpu()
-        ev_single = time.perf_counter() - t1
+        ev_single = None
+        if args.full:
+            t1 = time.perf_counter()  # one evaluation on an idle device through the plain call, host enqueue included (latency, not throughput)
+            res = full_catalog_topk(victim, ev_dev, ptr_dev, idx_dev, tg_dev, K=100, chunk=ev_chunk, to_host=False)
+            hit_counts(res["target_rank"], (10, 20, 50, 100)).cpu()
+            ev_single = time.perf_counter() - t1
         deg = np.diff(ptr)
         pairs = float((ds.n_items - deg[ev_users]).sum())
         flops = 2.0 * len(ev_users) * ds.n_items * args.dim
@@ -1119,7 +1150,7 @@ def worker(args, traffic_live=None):
                             + (f"; {world} replicas, one per GPU, slowest rank's time" if world > 1 else "")}
 
     mfma = None
-    if rank == 0 and world == 1 and not args.no_topk and not big and not collectives:
+    if args.full and rank == 0 and world == 1 and not args.no_topk and not big and not collectives:
         mfma = mfma_gemm_probe(dev)
     also = None
     if rank == 0 and world == 1 and not collectives and args.workload == "ml1m" and not args.no_also:
@@ -1170,6 +1201,7 @@ def worker(args, traffic_live=None):
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
             "data": "synthetic",
+            "full": bool(args.full),   # False: the headline figure's own legs only, the keys of the other legs are null
             "config": {"workload": workload_string(args.workload, ds.n_users, ds.n_items, ds.traindataSize, args.graph, nnz, args.dim, args.layers, B),
                        "parallelism": par, "mode": "replicas" if world > 1 else "single",
                        "backend": args.backend if collectives else None,

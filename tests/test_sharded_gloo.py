@@ -144,14 +144,16 @@ def test_slab_partition_covers_graph():
 
 
 def test_bench_self_launch_dry_run():
-    """`python bench.py --gpus 2` must start its own two workers (no torchrun) and print one JSON object."""
+    """`python bench.py --gpus 2` must start its own two workers (no torchrun) and print one JSON object.  The sharded `also` legs
+    belong to a --full run: the launcher hands the option on to its workers, a plain run has none of them."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], capture_output=True, text=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run", "--full"], capture_output=True, text=True,
                        timeout=300, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     d = json.loads(line)
     assert d["dry_run"] and d["n_gpus"] == 2 and d["rank_sum"] == 1.0 and d["parallel"] == "replicas" and d["scaling"] == "weak"
+    assert d["full"] is True
     # the strong-scaling jobs live in `also`: config 4 in the default form, then the SAME job in the three exchange forms the first
     # hardware run has to choose between (reduce_scatter_tensor / one-shot all-to-all + ordered sum / 1-D one-shot all-gather), each
     # with 1 and 4 row chunks, then the yelp shape
@@ -163,6 +165,8 @@ def test_bench_self_launch_dry_run():
         ("rows2d", "collective", "collective", 1), ("rows2d", "collective", "collective", 4), ("rows2d", "ordered", "collective", 1),
         ("rows2d", "ordered", "collective", 4), ("rows", "collective", "direct", 1), ("rows", "collective", "direct", 4)}
     assert bench.Deadline.EXIT_CODE != 0
+    plain, full = bench.parse(["--gpus", "2"]), bench.parse(["--gpus", "2", "--full"])
+    assert plain.no_also_sharded and not full.no_also_sharded and bench.parse(["--gpus", "2", "--full", "--no-also-sharded"]).no_also_sharded
     # a world that disagrees with --gpus is refused
     env2 = dict(env, RANK="0", WORLD_SIZE="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-run"], capture_output=True, text=True,
