@@ -911,6 +911,78 @@ int rk_ials_objective(int32_t n_rows, int32_t n_cols, int32_t d, const int32_t *
                       float alpha, float lambda, const float *X /*[n_rows*d]*/, const float *Y /*[n_cols*d]*/,
                       const double *GY /*[d*d]*/, double *partial /*[n_rows]*/, double *J /*[1]*/, void *stream);
 
+/* PGA attacker: projected gradient ascent on the fake profiles through a factorisation fitted by alternating least squares (Li,
+ * Wang, Singh and Vorobeychik 2016, "Data Poisoning Attacks on Factorization-Based Collaborative Filtering"), here through one
+ * sweep of the iALS surrogate above.  It has no counterpart in the reference; the definition is this:
+ *   state: R in [0, 1]^{A x I}, the inclusion strengths of the A fake users, the target columns pinned to 1.  The binarised
+ *   profile of row f: the n_t targets and the filler_num non-target items of largest R_fj, ties to the lower id, columns
+ *   ascending; every entry carries the rating fake_rating (an integer 1..127), so every fake row has n_t + filler_num entries;
+ *   surrogate: iALS (rk_ials_gram, rk_ials_half_sweep) on the real rating CSR with the A binarised rows appended, with its own
+ *   d, alpha, lambda.  Of the last sweep: Yo the item table the users were solved from, X all user rows (the fake rows last),
+ *   Yp the item table solved from X;
+ *   loss on Yp and the real rows of X: for target t the eligible users E_t are the real users with no stored entry at t;
+ *   s_uj = x_u . y+_j (the fp32 GEMM), the items u has rated excluded from the softmax; L = sum_t (1 / |E_t|) sum_{u in E_t}
+ *   [lse_j s_uj - s_ut].  lse and the softmax are worked out in double from the fp32 scores; D_uj = fl32((softmax_uj - [j = t]) /
+ *   |E_t|), exactly +0.0f at rated items and in the rows of users outside E_t; the loss terms stay doubles and are summed in a
+ *   fixed order.  g = D^T X_real ([I, d]) through the fp32 GEMM per block of users and target, the partial products added in
+ *   (target, block) order;
+ *   hypergradient through the last sweep, Yo held constant: wbar = fl(alpha * fake_rating), c_fj = 1 + wbar r_fj; under the linear
+ *   relaxation that takes an entry (f, j) from absent (r = 0) to present (r = 1) -- its weight wbar r in the systems, (1 + wbar) r
+ *   times the other side's row in the right-hand sides --
+ *     z_j = B_j^-1 g_j for every item, B_j the matrix rk_ials_half_sweep factorises for item j over the transpose, G from X;
+ *     M = sum_j z_j y+_j^T ([d, d], the fp32 GEMM);
+ *     h_f = (1 + wbar) sum_{j in f} z_j - (M + M^T) x_f - wbar sum_{j in f} [s+_fj z_j + (x_f . z_j) y+_j],  s+_fj = x_f . y+_j;
+ *     v_f = A_f^-1 h_f, A_f the matrix the user side factorises for fake row f, G from Yo;
+ *     grad_fj = (1 + wbar - wbar s+_fj)(x_f . z_j) + (1 + wbar - wbar so_fj)(yo_j . v_f),  so_fj = x_f . yo_j, for every f and j:
+ *   the exact derivative of L(Yp(X(R), R)) at the binary point.  It differentiates one sweep, not the converged fixed point;
+ *   update: with m = max |grad| (not 0): R <- clip(R - fl(lr * fl(grad / m)), 0, 1), one rounding per operation and no
+ *   contraction; a result that is not > 0 becomes +0.0f; m = 0 leaves R alone.  Then the targets are set to 1 and the profile
+ *   is selected again.
+ * recad_amd/attack/pga.py sequences these entries, rk_gemm_f32 and rk_pca_transpose.  All pointers are device pointers, every
+ * entry is asynchronous, none adds floats atomically, and two runs give the same bits. */
+#define RK_PGA_MAX_TARGETS 64
+/* rk_ials_half_sweep with the right-hand side of row u read from rhs[u * d ..] instead of b_u: A_u is built and factorised by
+ * the same device code (so to the same bits), order and status as there.
+ * RK_EINVAL with nothing launched and nothing written: n_rows or n_cols < 1, d or alpha out of range, a missing pointer. */
+int rk_ials_solve_rhs(int32_t n_rows, int32_t n_cols, int32_t d, const float *G, const int32_t *rowptr, const int32_t *col,
+                      const float *val, float alpha, const float *Y /*[n_cols*d]*/, const float *rhs /*[n_rows*d]*/,
+                      const int32_t *order /*[n_rows] or NULL*/, float *X_out /*[n_rows*d]*/, int32_t *status /*int32[2]*/,
+                      void *stream);
+/* A block of nb score rows, row b belonging to user user0 + b of the rating CSR: scores [nb * n_items] holds s_uj on entry and
+ * D_uj on return, terms[b] = (lse - s_ut) * inv_count in double (0.0 for a user with eligible[user] == 0, whose row of D is
+ * +0.0f).  One wave per row; the sums run lane-strided and then over the wave's butterfly: a fixed order.
+ * RK_EINVAL with nothing launched and nothing written: nb or n_items < 1, user0 < 0, a target outside [0, n_items), inv_count
+ * not a finite positive number, a missing pointer. */
+int rk_pga_loss(int32_t nb, int32_t n_items, float *scores /*[nb*n_items]*/, const int32_t *rowptr, const int32_t *col,
+                int32_t user0, int32_t target, const int32_t *eligible /*[n_users]*/, double inv_count, double *terms /*[nb]*/,
+                void *stream);
+/* out[0] = the sum of n doubles: thread t of one workgroup adds terms t, t + 256, ... in order, then the fixed tree. */
+int rk_pga_loss_sum(int64_t n, const double *terms, double *out /*[1]*/, void *stream);
+/* out[i] = ((parts[0][i] + parts[1][i]) + parts[2][i]) + ...: n_parts arrays of n floats added in order. */
+int rk_pga_add_blocks(int64_t n, int32_t n_parts, const float *parts /*[n_parts*n]*/, float *out /*[n]*/, void *stream);
+/* H[f] = h_f for the n_fake rows of the fake CSR (fptr, fcol): one workgroup per row.  s+ and q = x . z are d-long fmaf chains
+ * over the lanes and the wave's butterfly.  (1 + wbar) z_j - wbar s+ z_j cancels to one part in wbar on a fitted entry (s+ near
+ * 1), so the coefficient cf = fl(1 + fl(wbar fl(1 - s+))) is formed first; the sparse sum runs in column order,
+ * t += fl(fl(cf z_j) - fl(fl(wbar q) y+_j)), and h = fl(t - m), m the l-ordered sum of fl(fl(M_kl + M_lk) x_l), no contraction.
+ * RK_EINVAL with nothing launched and nothing written: a size < 1, d or wbar out of range, a missing pointer. */
+int rk_pga_user_adjoint(int32_t n_fake, int32_t n_items, int32_t d, const float *Z /*[I*d]*/, const float *Yp /*[I*d]*/,
+                        const float *Xf /*[A*d]*/, const float *M /*[d*d]*/, const int32_t *fptr /*[A+1]*/, const int32_t *fcol,
+                        float wbar, float *H /*[A*d]*/, void *stream);
+/* grad [A * I] as defined: four k-ordered fmaf chains of length d per element (x.z, x.y+, x.yo, yo.v), combined as
+ * (1 + wbar (1 - s+)) (x.z) + (1 + wbar (1 - so)) (yo.v) (the coefficients as in rk_pga_user_adjoint); eight fake rows held in
+ * LDS across a tile of 256 items.  gmax[0] = the bit pattern of max |grad| (an integer max: order-free), 0 for a zero gradient.
+ * RK_EINVAL with nothing launched and nothing written: a size < 1, d or wbar out of range, a missing pointer. */
+int rk_pga_grad(int32_t n_fake, int32_t n_items, int32_t d, const float *Xf, const float *V, const float *Z, const float *Yp,
+                const float *Yo, float wbar, float *grad /*[A*I]*/, uint32_t *gmax /*[1]*/, void *stream);
+/* The update (grad == NULL or gmax[0] == 0: none), the pinning of the targets and the selection, one workgroup per row of any
+ * length: a radix select over the bit patterns finds the filler_num-th largest non-target strength, an ordered compaction writes
+ * the n_targets + filler_num columns of row f ascending at fcol_out[f * (n_targets + filler_num) ..].  targets: distinct ids in
+ * [0, n_items) (the caller checks them).
+ * RK_EINVAL with nothing launched and nothing written: a size < 1, n_targets outside 1..RK_PGA_MAX_TARGETS, filler_num outside
+ * [0, n_items - n_targets], lr not a finite positive number (with grad), a missing pointer. */
+int rk_pga_step(int32_t n_fake, int32_t n_items, float *R /*[A*I]*/, const float *grad /*[A*I] or NULL*/, const uint32_t *gmax,
+                float lr, int32_t n_targets, const int32_t *targets, int32_t filler_num, int32_t *fcol_out, void *stream);
+
 /* SLIM victim: sparse linear item-item weights (Ning and Karypis 2011, "SLIM: Sparse Linear Methods for Top-N Recommender
  * Systems"): each item's column is an elastic-net regression on the other items with non-negative weights and a zero diagonal,
  * fitted by cyclic coordinate descent and repeatable to the bit.  It has no counterpart in the reference; the definition is this:

@@ -30,6 +30,7 @@ RK_ITEMKNN_MAX_BAND, RK_ITEMKNN_MAX_ITEMS, RK_ITEMKNN_MAX_USER_BLOCK = 39872, 16
 RK_EASE_MAX_ITEMS, RK_EASE_BLOCK_SMALL, RK_EASE_BLOCK_LARGE = 65536, 32, 64
 RK_EASE_BAD_GRAM, RK_EASE_NOT_SPD = 5, 6
 RK_IALS_MAX_DIM, RK_IALS_CHUNK, RK_IALS_GRAM_ROWS, RK_IALS_NOT_SPD = 128, 64, 256, 7
+RK_PGA_MAX_TARGETS = 64
 RK_SLIM_MAX_ITEMS, RK_SLIM_BAD_DIAG = 20464, 8
 RK_APR_MAX_DIM, RK_APR_MAX_BATCH = 256, 65536
 RK_APR_MAX_GROUP = 64     # members of one rk_apr_train_epoch_group call
@@ -331,6 +332,13 @@ _SIGNATURES = {
     "rk_ials_system": [_I32, _I32, _P, _P, _P, _P, _F, _P, _I32, _P, _P, _P, _P],
     "rk_ials_half_sweep": [_I32, _I32, _I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P],
     "rk_ials_objective": [_I32, _I32, _I32, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P, _P],
+    "rk_ials_solve_rhs": [_I32, _I32, _I32, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P],
+    "rk_pga_loss": [_I32, _I32, _P, _P, _P, _I32, _I32, _P, C.c_double, _P, _P],
+    "rk_pga_loss_sum": [_I64, _P, _P, _P],
+    "rk_pga_add_blocks": [_I64, _I32, _P, _P, _P],
+    "rk_pga_user_adjoint": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _F, _P, _P],
+    "rk_pga_grad": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _F, _P, _P, _P],
+    "rk_pga_step": [_I32, _I32, _P, _P, _P, _F, _I32, _P, _I32, _P, _P],
     "rk_slim_fit": [_I32, _P, _F, _I32, _P, _P, _P, _P, _P],
     "rk_apr_workspace": [_I32, _I32, _I32, _I64, _I32, C.POINTER(AprLayout)],
     "rk_apr_train_epoch": [C.POINTER(AprDesc), _P, _P, _P, _I64, _I32, _I32, _I32, _P, _P, _P],

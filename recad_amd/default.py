@@ -2,7 +2,8 @@
 
 Mirrors the keys and values of the reference's registry for the three victims, the random, average, segment, bandwagon, AUSH, AIA, AushPlus and UBA attackers,
 the PCASelectUsers defender (recad/default.py:103-221,223-228) and the implicit / explicit dataset and workflow knobs the
-hot path reads (recad/default.py:49-99,247-267).  Only what the path needs is present.
+hot path reads (recad/default.py:49-99,247-267).  Only what the path needs is present.  Entries marked build-specific (the
+later victims and defenders, the PGA attacker) have no counterpart there.
 """
 import logging
 import os
@@ -74,6 +75,11 @@ MODEL = {
                                     454, 835, 14, 537, 500, 486, 318, 754, 385, 218, 545, 154, 226, 301, 469, 92, 617, 728, 926, 651, 725,
                                     418, 435, 243, 595, 97, 130, 836, 91],
                 "budget": 6, "hops": "elementwise", "seed": None},
+        # build-specific (no reference counterpart): projected gradient ascent through one sweep of an iALS surrogate (Li, Wang,
+        # Singh and Vorobeychik 2016), attack/pga.py.  These values are choices, not tuned ones: nobody has measured which
+        # settings attack best.  seed_s None = the surrogate's item table is seeded from torch's global RNG at .I()
+        "pga": {"attack_num": 50, "filler_num": 36, "fake_rating": 5.0, "lr": 0.25, "factor_num_s": 16, "alpha_s": 40.0,
+                "reg_lambda_s": 10.0, "init_sweeps_s": 10, "sweeps_s": 2, "seed_s": None},
     },
     # recad/default.py:223-228; block / tol / max_iter / seed are this build's solver knobs (block None = 8, or 16 when kVals > 5)
     "defender": {"PCASelectUsers": {"kVals": 3, "attack_num": 50, "block": None, "tol": 1e-5, "max_iter": 300, "seed": SEED},

@@ -7,7 +7,7 @@ factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": vic
                         "multvae": victim.MultVAE},
              "attacker": {"aia": attack.AIA, "aush": attack.Aush, "aushplus": attack.AushPlus, "random": attack.RandomAttacker,
                           "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack,
-                          "uba": attack.UBA},
+                          "uba": attack.UBA, "pga": attack.PGA},
              "defender": {"PCASelectUsers": defense.PCASelectUsers, "KnnSelectUsers": defense.KnnSelectUsers,
                           "CatchSyncSelectUsers": defense.CatchSyncSelectUsers}}
 
