@@ -69,6 +69,14 @@ int rk_csr_schedule_build(int32_t n_rows, const int32_t *rowptr, int32_t class_s
  * n_words schedule words (what _upload sends to the device) into a host array */
 int rk_csr_schedule_build_host(int32_t n_rows, const int32_t *rowptr_host, int32_t class_split, int32_t dim,
                                rk_schedule_t *out, int32_t *n_blocks, int64_t *n_words, int64_t *scratch_words);
+/* the same with the schedule's FORM asked for: waves = waves per workgroup (0 = choose, 4, 8, 16), seg_nnz = nonzeros per segment
+ * (0 = choose, 64, 128), pack = 0 (pack short rows when a quarter of the rows is short), 1 (pack every row of <= dim/4 nonzeros;
+ * dims 32 / 64 / 128 only) or -1 (never); any other value is RK_EINVAL.  All zero = rk_csr_schedule_build_host, word for word.
+ * The shipped builder only ever picks 4 or 8 waves by the graph's size; this entry is how the tests reach every instantiation the
+ * SpMM launch dispatches to.  Graph dropout is instantiated for 4 and 8 waves: a dropout launch on a 16-wave schedule is refused. */
+int rk_csr_schedule_build_host_ex(int32_t n_rows, const int32_t *rowptr_host, int32_t class_split, int32_t dim,
+                                  int32_t waves, int32_t seg_nnz, int32_t pack,
+                                  rk_schedule_t *out, int32_t *n_blocks, int64_t *n_words, int64_t *scratch_words);
 int rk_csr_schedule_words(rk_schedule_t sched, int32_t *host_out /*[n_words]*/);
 int rk_csr_schedule_upload(rk_schedule_t sched, int32_t *wave_desc, void *stream);
 int rk_csr_schedule_destroy(rk_schedule_t sched);
@@ -83,6 +91,9 @@ int rk_build_norm_adj(int32_t n_users, int32_t n_items, const int32_t *r_ptr, co
 
 /* Y = A.X (+ add).  Replaces torch.sparse.mm(g, all_emb), recad/model/victim/lightgcn.py:107.
  * X, add (nullable), Y: device float[n_rows*dim], row-major; n_rows*dim*4 < 4 GiB.
+ * X must be FINITE: the lanes of a wave that have no entry left gather row 0 of X and multiply it by zero, so an Inf / NaN in
+ * X[0] reaches rows that have no entry in column 0 (torch.sparse.mm would not do that).  A non-finite row that is neither row 0
+ * nor referenced by a stored entry is never read.  The same holds for rk_spmm_csr_ex and the LightGCN handle's tables.
  * scratch: device int32[scratch_words] of rk_csr_schedule_build (NULL when that was 0). */
 int rk_spmm_csr(int32_t n_rows, const int32_t *rowptr, const int32_t *col, const float *val,
                 const int32_t *wave_desc, int32_t n_blocks, int32_t *scratch, int32_t dim, const float *x,

@@ -22,29 +22,45 @@ struct rk_schedule {
     size_t scratch_words() const { return n_long ? (size_t)((n_long + 3) & ~3) + (size_t)n_slots * (size_t)dim : 0; }
 };
 
+// The schedule's FORM asked for (rk_csr_schedule_build_host_ex: how the tests reach every kernel instantiation spmm_launch
+// dispatches to); all zero = the shipped choice.  In a tuning build a zero field still takes its RK_* knob.
+struct rk_schedule_request {
+    int32_t waves = 0;    // waves per workgroup: 0 = choose (spmm_waves_for), 4, 8, 16
+    int32_t seg_nnz = 0;  // nonzeros per segment: 0 = choose, 64, 128
+    int32_t pack = 0;     // 0 = pack when a quarter of the rows is short, 1 = pack every row of <= dim/4 nonzeros, -1 = never
+};
+
 // rowptr: HOST array of n_rows + 1 entries
-inline int csr_schedule_build_host_body(int32_t n_rows, const int32_t *rowptr, int32_t class_split, int32_t dim,
+inline int csr_schedule_build_host_body(int32_t n_rows, const int32_t *rowptr, int32_t class_split, int32_t dim, const rk_schedule_request &rq,
                                         rk_schedule_t *out, int32_t *n_blocks, int64_t *n_words, int64_t *scratch_words);
 // what the C-ABI entry points call: no C++ exception unwinds through extern "C" (see host/lds_plan_host.h)
 inline int csr_schedule_build_host_impl(int32_t n_rows, const int32_t *rowptr, int32_t class_split, int32_t dim,
-                                        rk_schedule_t *out, int32_t *n_blocks, int64_t *n_words, int64_t *scratch_words)
+                                        rk_schedule_t *out, int32_t *n_blocks, int64_t *n_words, int64_t *scratch_words,
+                                        const rk_schedule_request &rq = rk_schedule_request())
 {
     try {
-        return csr_schedule_build_host_body(n_rows, rowptr, class_split, dim, out, n_blocks, n_words, scratch_words);
+        return csr_schedule_build_host_body(n_rows, rowptr, class_split, dim, rq, out, n_blocks, n_words, scratch_words);
     } catch (const std::bad_alloc &) {
         RK_FAIL(RK_ENOMEM, "rk_csr_schedule_build: out of host memory");
     } catch (const std::exception &e) {
         RK_FAIL(RK_EINVAL, "rk_csr_schedule_build: %s", e.what());
     }
 }
-inline int csr_schedule_build_host_body(int32_t n_rows, const int32_t *rowptr, int32_t class_split, int32_t dim,
+inline int csr_schedule_build_host_body(int32_t n_rows, const int32_t *rowptr, int32_t class_split, int32_t dim, const rk_schedule_request &rq,
                                         rk_schedule_t *out, int32_t *n_blocks, int64_t *n_words, int64_t *scratch_words)
 {
     if (n_rows <= 0 || !rowptr || !out || !n_blocks || !n_words || !scratch_words || class_split < 0 || class_split > n_rows || dim <= 0 || dim > 256)
         RK_FAIL(RK_EINVAL, "rk_csr_schedule_build: bad arguments");
+    if (rq.waves != 0 && rq.waves != 4 && rq.waves != 8 && rq.waves != 16)
+        RK_FAIL(RK_EINVAL, "rk_csr_schedule_build_host_ex: waves per workgroup are 0 (choose), 4, 8 or 16, not %d", (int)rq.waves);
+    if (rq.seg_nnz != 0 && rq.seg_nnz != 64 && rq.seg_nnz != 128)
+        RK_FAIL(RK_EINVAL, "rk_csr_schedule_build_host_ex: a segment is 0 (choose), 64 or 128 nonzeros, not %d", (int)rq.seg_nnz);
+    if (rq.pack < -1 || rq.pack > 1) RK_FAIL(RK_EINVAL, "rk_csr_schedule_build_host_ex: pack is 0 (choose), 1 or -1, not %d", (int)rq.pack);
+    if (rq.pack == 1 && !(dim == 32 || dim == 64 || dim == 128))
+        RK_FAIL(RK_EINVAL, "rk_csr_schedule_build_host_ex: only dims 32, 64 and 128 pack short rows, not %d", (int)dim);
     // short rows are packed one per lane group (dim/4 lanes): only the vector kernels with >= 2 groups do that
     static const int no_pack = RK_TUNE_INT("RK_SPMM_NO_PACK", 0);
-    int pack_groups = (!no_pack && (dim == 32 || dim == 64 || dim == 128)) ? 256 / dim : 1;
+    int pack_groups = (rq.pack >= 0 && (rq.pack == 1 || !no_pack) && (dim == 32 || dim == 64 || dim == 128)) ? 256 / dim : 1;
     int pack_max = pack_groups > 1 ? dim / 4 : -1;  // nonzeros a lane group reads in one chunk
     const int32_t *rp = rowptr;
     // rows by degree, descending, stable in row id (counting sort) => deterministic schedule
@@ -55,21 +71,21 @@ inline int csr_schedule_build_host_body(int32_t n_rows, const int32_t *rowptr, i
     for (size_t k = 1; k < cnt.size(); ++k) cnt[k] += cnt[k - 1];
     for (int32_t r = 0; r < n_rows; ++r) order[(size_t)cnt[(size_t)(maxdeg - (rp[r + 1] - rp[r]))]++] = r;
 
-    if (pack_groups > 1) {
+    if (pack_groups > 1 && rq.pack == 0) {
         // packing uses a separate kernel instantiation (the packed path costs the plain one ~2 %): only
         // worth it when a good share of the rows is short (the reference's as-is test-edge graphs)
         int32_t n_short = 0;
         for (int32_t r = 0; r < n_rows; ++r) n_short += (rp[r + 1] - rp[r] <= pack_max) ? 1 : 0;
         if (4LL * n_short < n_rows) { pack_groups = 1; pack_max = -1; }
     }
-    const int kSpmmWaves = spmm_waves_for((long long)rp[n_rows]);
+    const int kSpmmWaves = rq.waves ? rq.waves : spmm_waves_for((long long)rp[n_rows]);
     // Nonzeros per segment (= per wave).  A row of 65..128 nonzeros is two waves + an LDS combine at 64 but one
     // wave at 128: when most of the nonzeros sit in such rows (ml1m's train graph: 97 per row on average) 128
     // is worth 7 % of a train step (106.4 -> 99.2 us); on short-row graphs it only lengthens the tail (the
     // reference's as-is graph: 46.7 -> 50.0 us), and above 8 M nonzeros it measured flat.  RK_SEG_NNZ overrides.
     static const int seg_env = RK_TUNE_INT("RK_SEG_NNZ", 0) ? std::max(16, RK_TUNE_INT("RK_SEG_NNZ", 0)) : 0;
-    int seg_nnz = seg_env ? seg_env : kSegNnz;
-    if (!seg_env && kSpmmWaves == 4) {
+    int seg_nnz = rq.seg_nnz ? rq.seg_nnz : seg_env ? seg_env : kSegNnz;
+    if (!rq.seg_nnz && !seg_env && kSpmmWaves == 4) {
         long long over = 0;
         for (int32_t r = 0; r < n_rows; ++r) { const int32_t k = rp[r + 1] - rp[r]; if (k > kSegNnz) over += k; }
         if (2 * over >= (long long)rp[n_rows]) seg_nnz = 2 * kSegNnz;

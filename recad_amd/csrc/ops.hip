@@ -68,6 +68,15 @@ RK_EXPORT int rk_csr_schedule_build_host(int32_t n_rows, const int32_t *rowptr, 
     return csr_schedule_build_host_impl(n_rows, rowptr, class_split, dim, out, n_blocks, n_words, scratch_words);
 }
 
+RK_EXPORT int rk_csr_schedule_build_host_ex(int32_t n_rows, const int32_t *rowptr, int32_t class_split, int32_t dim,
+                                            int32_t waves, int32_t seg_nnz, int32_t pack,
+                                            rk_schedule_t *out, int32_t *n_blocks, int64_t *n_words, int64_t *scratch_words)
+{
+    rk_schedule_request rq;
+    rq.waves = waves; rq.seg_nnz = seg_nnz; rq.pack = pack;
+    return csr_schedule_build_host_impl(n_rows, rowptr, class_split, dim, out, n_blocks, n_words, scratch_words, rq);
+}
+
 RK_EXPORT int rk_csr_schedule_build(int32_t n_rows, const int32_t *rowptr, int32_t class_split, int32_t dim, void *stream,
                                     rk_schedule_t *out, int32_t *n_blocks, int64_t *n_words, int64_t *scratch_words)
 {

@@ -44,7 +44,7 @@ struct SpmmArgs {
     const int4 *wave_desc;  // per wave: {row, e_begin, e_end, n_segments if row leader else 0}
     int n_blocks;
     int d;
-    const float *x;  // [n_rows, d] row-major; n_rows*d*4 < 4 GiB (32-bit byte offsets)
+    const float *x;  // [n_rows, d] row-major; n_rows*d*4 < 4 GiB (32-bit byte offsets).  FINITE: padding lanes add 0 * x[0] (recad_hip.h)
     int dbg;
     // long rows (> waves-per-workgroup segments): arrival counters int[n_long] (zero between launches: the last
     // arriver resets its counter) followed, 16-byte aligned, by the partial-sum slots float[n_slots][d].
@@ -124,9 +124,15 @@ __device__ __forceinline__ float drop_val(const DropCtx &c, int e, float v)
     return rk_drop_keep(c.seed_step, id, c.thresh24) ? v * c.inv_keep : 0.f;
 }
 
+// One term of a row's chain: acc = fma(a, x, acc), asked for BY NAME.  Written as `acc += a * x` the contraction was the compiler's
+// choice per inlined copy: the same kernel fused the products of one gather_round size and rounded those of another (dim 32: the
+// 4-deep rounds rounded, the 8-deep fused; dim 64 the other way round -- tests/test_spmm_csr_forms_gpu.py), so a row's bits
+// depended on which unroll depth its length fell into, and the frontier-filtered instantiation (4-deep rounds only) could not
+// reproduce the unfiltered one on an all-ones bitmap.
 __device__ __forceinline__ float4 f4_fma(float a, float4 x, float4 acc)
 {
-    acc.x += a * x.x; acc.y += a * x.y; acc.z += a * x.z; acc.w += a * x.w;
+    acc.x = __builtin_fmaf(a, x.x, acc.x); acc.y = __builtin_fmaf(a, x.y, acc.y);
+    acc.z = __builtin_fmaf(a, x.z, acc.z); acc.w = __builtin_fmaf(a, x.w, acc.w);
     return acc;
 }
 __device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
@@ -479,7 +485,7 @@ static __global__ __launch_bounds__(1024) void spmm_csr_generic_kernel(const Spm
         const float av = drop_val(dc, e, a.val[e]);
 #pragma unroll
         for (int k = 0; k < kGenMaxC; ++k)
-            if (k * 64 + lane < d) acc[k] += av * x[k * 64 + lane];
+            if (k * 64 + lane < d) acc[k] = __builtin_fmaf(av, x[k * 64 + lane], acc[k]);   // (by name: see f4_fma)
     }
 #pragma unroll
     for (int k = 0; k < kGenMaxC; ++k) part[w][k * 64 + lane] = acc[k];

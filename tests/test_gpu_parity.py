@@ -454,16 +454,14 @@ def test_workflow_end_to_end_on_device(gpu_device):
             assert abs(rows[:, 2 + i].mean() - res[f"HR@{k}"]) < 1e-12, (name, k)
 
 
-def test_lightgcn_marked_block_list_same_bits(gpu_device):
-    """Row-gather path, L >= 3: the row-filtered last forward layer starts only the schedule's workgroups that hold a minibatch
-    row (listed by the launch before it: desc.row_blocks, spmm.h SpmmArgs::blk_mode) instead of every workgroup.  Which
-    workgroups run does not change any sum: with the ordered scatter the trained tables and losses are BIT-identical to a
-    victim without the list -- across epochs, a ragged last batch, plain launches and hipGraph replays, L = 3 and 4."""
+def marked_block_list_same_bits(gpu_device, seed_schedule=None, B=32):
+    """the body of test_lightgcn_marked_block_list_same_bits; seed_schedule(model) may put a schedule of another form into the
+    graph's cache before the handle is built (tests/test_spmm_csr_forms_gpu.py: 8 waves, packing forced on)"""
     from recad_amd import model
     g = G.load("lightgcn_game_d64_tg")
     U, I = int(g["n_users"]), int(g["n_items"])
     rng = np.random.default_rng(17)
-    B, n = 32, 32 * 7 + 5    # (the list is used where it at least halves the launch: 3 B + long-row pieces <= half the schedule's workgroups)
+    n = B * 7 + 5    # (the list is used where it at least halves the launch: 3 B + long-row pieces <= half the schedule's workgroups)
     cols = [torch.from_numpy(rng.integers(0, hi, n)).to(gpu_device) for hi in (U, I, I)]
     for layers in (3, 4):
         for graph_steps in (0, 32):
@@ -476,6 +474,8 @@ def test_lightgcn_marked_block_list_same_bits(gpu_device):
                 m.embedding_item.weight.data.copy_(torch.from_numpy(i0))
                 m = m.to(gpu_device)
                 m.use_lds, m.use_block_list, m.graph_steps = False, use_list, graph_steps
+                if seed_schedule is not None:
+                    seed_schedule(m)
                 l1 = m._run_epoch(*cols, B).sum(dim=1).double().cpu().numpy().copy()
                 l2 = m._run_epoch(*(c[: 3 * B] for c in cols), B).sum(dim=1).double().cpu().numpy().copy()
                 assert (m._ws.get("row_blocks") is not None) == use_list
@@ -485,6 +485,14 @@ def test_lightgcn_marked_block_list_same_bits(gpu_device):
                 outs.append((l1, l2, m.embedding_user.weight.detach().cpu().numpy().copy(), m.embedding_item.weight.detach().cpu().numpy().copy()))
             for a_, b_ in zip(*outs):
                 assert np.array_equal(a_, b_), (layers, graph_steps)
+
+
+def test_lightgcn_marked_block_list_same_bits(gpu_device):
+    """Row-gather path, L >= 3: the row-filtered last forward layer starts only the schedule's workgroups that hold a minibatch
+    row (listed by the launch before it: desc.row_blocks, spmm.h SpmmArgs::blk_mode) instead of every workgroup.  Which
+    workgroups run does not change any sum: with the ordered scatter the trained tables and losses are BIT-identical to a
+    victim without the list -- across epochs, a ragged last batch, plain launches and hipGraph replays, L = 3 and 4."""
+    marked_block_list_same_bits(gpu_device)
 
 
 def test_eval_session_matches_full_catalog_topk(gpu_device):

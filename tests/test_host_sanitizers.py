@@ -2,7 +2,8 @@
 under AddressSanitizer + UBSan and under ThreadSanitizer (CPU builds only): `make -C recad_amd/csrc host-asan
 host-tsan` compiles tests/tools/host_builders_driver.cpp, which runs both builders on a stress set of graphs from several
 caller threads at once -- a dozen of them with the plan's FORM forced (slice widths up to 16, chunk caps up to 512: the builder's
-paths the shipped choice never takes).  Both runs must be clean AND produce the product library's words bit for bit."""
+paths the shipped choice never takes), a dozen with the schedule's (rk_csr_schedule_build_host_ex: 8 and 16 waves, 128-entry
+segments, packing forced on and off).  Both runs must be clean AND produce the product library's words bit for bit."""
 import ctypes as C
 import os
 import subprocess
@@ -12,6 +13,7 @@ import pytest
 
 from recad_amd import _lib, synth
 from tests import _lds_restate as R
+from tests import _spmm_restate as S
 from tests._lds_restate import norm_adj_csr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,8 +21,9 @@ CSRC = os.path.join(ROOT, "recad_amd", "csrc")
 
 
 def _graphs():
-    """(U, I, dim, n_cu, split, rowptr, col, val[, (slice_items, slice_users, chunk_cap)]): the reference-shaped graphs + the randomised family of
-    tests/tools/spmm_lds_stress.py (tiny classes, empty rows, full rows, dense and sparse; every dim % 4 == 0 up to 256)."""
+    """(U, I, dim, n_cu, split, rowptr, col, val[, (slice_items, slice_users, chunk_cap) or None[, (waves, seg_nnz, pack)]]): the
+    reference-shaped graphs + the randomised family of tests/tools/spmm_lds_stress.py (tiny classes, empty rows, full rows, dense and
+    sparse; every dim % 4 == 0 up to 256)."""
     out = []
     for shape, dims in (("tiny", (16, 32, 64, 128, 256)), ("ml1m", (64,))):
         data = synth.make(shape)
@@ -58,6 +61,12 @@ def _graphs():
         else:
             U, I, rp, col, val = R.graph(name)
         out.append((U, I, d, n_cu, 1, rp, col, val, force))
+    # forced schedules (rk_csr_schedule_build_host_ex) on the case graphs of tests/test_spmm_csr_forms_*.py: not bipartite, so no plan
+    for d, W, seg, pack, split in (S.VEC_FORMS[1], S.VEC_FORMS[4], S.VEC_FORMS[11], S.VEC_FORMS[23], S.VEC_FORMS[14]) + S.PACK_FORMS[1::3] \
+            + S.GEN_FORMS[2::4] + S.SPLIT_FORMS[1:4]:
+        rp, col, val, _ = S.case_graph(d, W, seg)
+        n = len(rp) - 1
+        out.append((n // 2, n - n // 2, d, 8, split, rp, col, val, None, (W, seg, pack)))
     return out
 
 
@@ -65,6 +74,7 @@ def _product_words(g):
     """the shipped library's builders on the same graph (pure host entry points: no GPU needed)"""
     U, I, d, n_cu, split, rp, col, val = g[:8]
     force = g[8] if len(g) > 8 else None
+    sform = g[9] if len(g) > 9 else (0, 0, 0)
     L = _lib.lib()
     rp_, col_, val_ = (np.ascontiguousarray(a) for a in (rp.astype(np.int32), col.astype(np.int32), val.astype(np.float32)))
     plan, n_words, info = C.c_void_p(), C.c_int64(0), _lib.LdsInfo()
@@ -79,8 +89,12 @@ def _product_words(g):
         _lib.check(L.rk_lds_plan_words(plan, pw.ctypes.data_as(C.c_void_p)), "rk_lds_plan_words")
         L.rk_lds_plan_destroy(plan)
     sched, n_blocks, sw, scr = C.c_void_p(), C.c_int32(0), C.c_int64(0), C.c_int64(0)
-    _lib.check(L.rk_csr_schedule_build_host(U + I, rp_.ctypes.data_as(C.c_void_p), U if split else 0, d, C.byref(sched), C.byref(n_blocks),
-                                            C.byref(sw), C.byref(scr)), "rk_csr_schedule_build_host")
+    if len(g) > 9:
+        _lib.check(L.rk_csr_schedule_build_host_ex(U + I, rp_.ctypes.data_as(C.c_void_p), U if split else 0, d, *sform, C.byref(sched),
+                                                   C.byref(n_blocks), C.byref(sw), C.byref(scr)), "rk_csr_schedule_build_host_ex")
+    else:
+        _lib.check(L.rk_csr_schedule_build_host(U + I, rp_.ctypes.data_as(C.c_void_p), U if split else 0, d, C.byref(sched), C.byref(n_blocks),
+                                                C.byref(sw), C.byref(scr)), "rk_csr_schedule_build_host")
     words = np.zeros(sw.value, dtype=np.int32)
     _lib.check(L.rk_csr_schedule_words(sched, words.ctypes.data_as(C.c_void_p)), "rk_csr_schedule_words")
     L.rk_csr_schedule_destroy(sched)
@@ -95,7 +109,8 @@ def stress_set(tmp_path_factory):
         f.write(np.int32(len(gs)).tobytes())
         for g in gs:
             U, I, d, n_cu, split, rp, col, val = g[:8]
-            f.write(np.asarray([U, I, d, n_cu, split, len(col), *(g[8] if len(g) > 8 else (0, 0, 0))], dtype=np.int32).tobytes())
+            f.write(np.asarray([U, I, d, n_cu, split, len(col), *((g[8] if len(g) > 8 else None) or (0, 0, 0)), *(g[9] if len(g) > 9 else (0, 0, 0))],
+                               dtype=np.int32).tobytes())
             f.write(rp.astype(np.int32).tobytes()); f.write(col.astype(np.int32).tobytes()); f.write(val.astype(np.float32).tobytes())
     return gs, path, [_product_words(g) for g in gs]
 
@@ -129,6 +144,8 @@ def test_host_builders_under_sanitizers(san, stress_set, tmp_path):
         got = np.frombuffer(buf[o:o + 4 * nsw], dtype=np.int32); o += 4 * nsw
         assert nb == n_blocks and sc == scr and np.array_equal(got, sw), ("schedule differs", g[:5])
         n_plans += npw > 0
-    n_forced = sum(1 for g, w in zip(gs, want) if len(g) > 8 and len(w[0]) > 0)
+    n_forced = sum(1 for g, w in zip(gs, want) if len(g) > 8 and g[8] is not None and len(w[0]) > 0)
     assert n_forced >= 12      # (edge at dim 12 with 8-float slices: refused by both, like any graph that does not qualify)
+    n_sched = [g[9] for g in gs if len(g) > 9]
+    assert len(n_sched) >= 12 and {f[0] for f in n_sched} == {4, 8, 16} and {f[1] for f in n_sched} == {64, 128} and {f[2] for f in n_sched} == {-1, 1}
     assert o == len(buf) and n_plans >= 20     # (graphs whose tables do not fit a CU's LDS give no plan: still scheduled)

@@ -4,7 +4,8 @@
 // with the product library's.  Built by `make -C recad_amd/csrc host-asan host-tsan`; never part of librecad_hip.so.
 //
 // input file : int32 n_graphs, then per graph: int32 U, I, dim, n_cu, class_split_flag, nnz, slice_items, slice_users, chunk_cap (the
-//              plan's form, 0 = choose: rk_lds_plan_build_host_ex); int32 rowptr[U+I+1]; int32 col[nnz]; float val[nnz]
+//              plan's form, 0 = choose: rk_lds_plan_build_host_ex), waves, seg_nnz, pack (the schedule's form, 0 = choose:
+//              rk_csr_schedule_build_host_ex); int32 rowptr[U+I+1]; int32 col[nnz]; float val[nnz]
 // output file: per graph: int64 n_plan_words, int32 plan_words[...], int64 n_sched_words, int32 n_blocks, int64 scratch_words, int32 sched_words[...]
 #include <stdio.h>
 
@@ -18,6 +19,7 @@ thread_local char rk_err_buf[512] = "";
 
 struct Graph {
     int32_t U, I, dim, n_cu, split, nnz, slice_items, slice_users, chunk_cap;
+    rk_schedule_request rq;
     std::vector<int32_t> rowptr, col;
     std::vector<float> val;
     std::vector<int32_t> plan, sched;
@@ -43,7 +45,7 @@ static void run_one(Graph &g)
     }
     rk_schedule_t sc = nullptr;
     int64_t sw = 0;
-    g.rc = csr_schedule_build_host_impl(g.U + g.I, g.rowptr.data(), g.split ? g.U : 0, g.dim, &sc, &g.n_blocks, &sw, &g.scratch_words);
+    g.rc = csr_schedule_build_host_impl(g.U + g.I, g.rowptr.data(), g.split ? g.U : 0, g.dim, &sc, &g.n_blocks, &sw, &g.scratch_words, g.rq);
     if (g.rc) return;
     g.sched = sc->desc;
     const int32_t hdr[4] = {sc->n_long, sc->n_slots, sc->dim, (int32_t)(sc->packed.size() / 4)};
@@ -64,10 +66,11 @@ int main(int argc, char **argv)
     if (!read_all(f, &n, 4) || n <= 0 || n > 100000) { fprintf(stderr, "bad header\n"); return 2; }
     std::vector<Graph> gs((size_t)n);
     for (Graph &g : gs) {
-        int32_t h[9];
+        int32_t h[12];
         if (!read_all(f, h, sizeof(h))) { fprintf(stderr, "truncated input\n"); return 2; }
         g.U = h[0]; g.I = h[1]; g.dim = h[2]; g.n_cu = h[3]; g.split = h[4]; g.nnz = h[5];
         g.slice_items = h[6]; g.slice_users = h[7]; g.chunk_cap = h[8];
+        g.rq.waves = h[9]; g.rq.seg_nnz = h[10]; g.rq.pack = h[11];
         g.rowptr.resize((size_t)g.U + g.I + 1); g.col.resize((size_t)g.nnz); g.val.resize((size_t)g.nnz);
         if (!read_all(f, g.rowptr.data(), 4 * g.rowptr.size()) || !read_all(f, g.col.data(), 4 * g.col.size()) || !read_all(f, g.val.data(), 4 * g.val.size())) {
             fprintf(stderr, "truncated input\n");
