@@ -779,6 +779,81 @@ int rk_itemknn_pair_scores(int32_t n_items, int32_t n_users, int32_t k, const in
                            const int32_t *rowptr, const int32_t *col, const float *val, const int64_t *users /*[n]*/,
                            const int64_t *items /*[n]*/, int64_t n, float *out /*[n]*/, void *stream);
 
+/* RP3beta victim: the random-walk item-item recommender (P3alpha: Cooper, Lee, Radzik and Siantos 2014; RP3beta: Christoffel,
+ * Paudel, Newell and Bernstein 2015; Paudel et al. 2017), exact in any accumulation order and repeatable to the bit.  It has no
+ * counterpart in the reference; the definition is this:
+ *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending) and its
+ *   transpose colptr / crow / cval (rk_pca_transpose); q_ui = (int) val; r_u = sum_j q_uj as int64; n_i = the number of raters
+ *   of item i = colptr[i + 1] - colptr[i]; alpha and beta finite doubles in [0, 4]; 1 <= k <= RK_KNN_MAX_K;
+ *   U < RK_RP3_MAX_USERS = 2^23, so that n_i * 2^40 < 2^63;
+ *   steps: for a stored entry (u, j), p = (q_uj / r_u)^alpha in double and P_uj = max(1, rint(2^40 * p)) as int64: the
+ *   transition probability of the walk's second step as a 40-bit fixed-point integer.  When alpha is exactly 1, p is the IEEE
+ *   quotient and pow is not called; when alpha is exactly 0, p = 1; with these two cases P3 at alpha = 1 is reproducible across
+ *   math libraries to the bit; otherwise p = pow(q_uj / r_u, alpha);
+ *   factors: fa_i = n_i^-alpha and fb_j = n_j^-beta in double, both 0 for an item nobody rated; exponent 1 is the IEEE quotient
+ *   1.0 / n, exponent 0 is 1, otherwise pow((double) n, -exponent);
+ *   dots: S_ij = sum over the users u with q_ui > 0 of P_uj, in unsigned 64-bit integers, for j != i: the first step of the walk
+ *   is binarised (item i moves to each of its n_i raters with probability 1 / n_i), as in the usual implementation;
+ *   weight: w_ij = (float)((((double) S_ij * fa_i) * fb_j) * 2^-40): one conversion of S to double (round to nearest), three
+ *   double multiplies in that order, one rounding to fp32 with gradual underflow, no contraction;
+ *   neighbours of item i: the candidates are every j != i with S_ij > 0, ordered by the 64-bit key
+ *   (bits of w) << 32 | (0xFFFFFFFF - j) descending, that is (w descending, j ascending), ItemKNN's key; k_eff = min(k, I - 1);
+ *   the first k_eff candidates fill slots t = 0, 1, ... of item i; layout slot-major as for ItemKNN: nbr_id[t * n_items + i]
+ *   (int32), nbr_w[t * n_items + i] (float32); unused slots hold -1 and +0.0f; every slot is written;
+ *   score(u, j) = the sum of fl(w_ij * (float) q_ui) over the items i that u has rated and whose kept list contains j: fp32,
+ *   taken in ascending order of i, starting from +0.0f, no contraction.  Items u has rated are scored like any other; a user
+ *   with no items scores +0.0f everywhere.
+ * Fixed point because the dots are sums of probabilities: floats added by atomics would depend on arrival order, ordered sums
+ * would serialise the workgroup; integers added by 64-bit LDS atomics are exact in any order, so the tables do not depend on
+ * `band`, `order` or the schedule.  The quantisation moves a weight by less than 2^-41 / p_min relative, far below the final fp32
+ * rounding.
+ * Each term carries one rounding more than w, and the sum carries (m - 1) more for m terms: every score lies within
+ * (m + c) * 2^-24 * sum of the terms of the float64 evaluation of the same tables (the same kept ids, w before its rounding to
+ * fp32), c = 2: m + 1 fp32 roundings in all, and one more unit covers the second-order terms while m <= 4094
+ * (tests/_rp3_restate.py counts m per score).
+ * Not built: the row normalisation of the kept weights some implementations add, the personalised PageRank form.
+ * recad_amd/victim/rp3beta.py drives these entries.  All pointers are device pointers. */
+/* Candidate items whose 64-bit accumulators one neighbour workgroup holds at once: 8 * band bytes plus ItemKNN's selection
+ * scratch (4160 bytes) within the 160 KiB of a CU's LDS less the 64 bytes every kernel here leaves free.  Also the widest band of
+ * rk_rp3_scores (4 bytes a column there). */
+#define RK_RP3_MAX_BAND 19904
+#define RK_RP3_MAX_USERS 8388608
+/* P[e] of every stored entry (int64 [nnz], in CSR order) and r[u] (int64 [U]).  One wave per row, one pass.  Asynchronous.
+ * RK_EINVAL with nothing launched and nothing written: alpha outside [0, 4] or not finite, n_users >= RK_RP3_MAX_USERS, a
+ * missing pointer. */
+int rk_rp3_steps(int32_t n_users, const int32_t *rowptr, const float *val, double alpha, int64_t *P /*[nnz]*/, int64_t *r /*[U]*/,
+                 void *stream);
+/* fa[i], fb[i] (double [I]) from the transpose's column pointers.  Asynchronous.  RK_EINVAL with nothing launched and nothing
+ * written: alpha or beta outside [0, 4] or not finite, a missing pointer. */
+int rk_rp3_factors(int32_t n_items, const int32_t *colptr, double alpha, double beta, double *fa /*[I]*/, double *fb /*[I]*/,
+                   void *stream);
+/* The neighbour tables of every item from the CSR's rowptr / col, P (any table of positive int64 in CSR order whose column sums
+ * stay below 2^63), the transpose's colptr / crow, fa and fb.  One workgroup per item; the dots of `band` candidate items at a
+ * time sit in LDS as 64-bit integers, added with LDS atomics; selection as in rk_itemknn_neighbors.
+ * band: 0 = automatic (the items in equal bands of at most 4096), else a multiple of 64 in 64..RK_RP3_MAX_BAND.  order ([I] or
+ * NULL) as in rk_itemknn_neighbors: results do not depend on it, an entry outside [0, I) is skipped.  Every slot of both tables
+ * is written.  Asynchronous.  RK_EINVAL with nothing launched and nothing written: k or band out of range,
+ * n_users >= RK_RP3_MAX_USERS, a missing pointer. */
+int rk_rp3_neighbors(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const int64_t *P /*[nnz]*/,
+                     const int32_t *colptr, const int32_t *crow, const double *fa, const double *fb, int32_t k, int32_t band,
+                     const int32_t *order /*[I] or NULL*/, int32_t *nbr_id /*[k*I]*/, float *nbr_w /*[k*I]*/, void *stream);
+/* out[b * n_items + j] = score(user_ids[b], j) for b in [0, nb), every j: every element of out is written.  One wave per entry
+ * of user_ids, with an fp32 row of one band of columns in LDS; the wave walks the user's items in ascending order and the slots
+ * of each item's list across its lanes (the ids of one list must be distinct, as the fit leaves them).  A catalogue wider than
+ * the band is so many passes; there is no catalogue cap.  band: 0 = automatic (equal bands of at most 8192), else a multiple of
+ * 64 in 64..RK_RP3_MAX_BAND.  user_ids ([nb], int32; repeats allowed): an id outside [0, U) scores like a user with no items.
+ * Asynchronous; nb = 0 launches nothing.  RK_EINVAL with nothing launched and nothing written: k or band out of range, a missing
+ * pointer. */
+int rk_rp3_scores(int32_t n_users, int32_t n_items, int32_t k, const int32_t *nbr_id, const float *nbr_w, const int32_t *rowptr,
+                  const int32_t *col, const float *val, int32_t nb, const int32_t *user_ids, int32_t band,
+                  float *out /*[nb * n_items]*/, void *stream);
+/* out[p] = score(users[p], items[p]), p in [0, n): the same sum in the same order, so the same bits as the matrix entry.  A
+ * pair whose user or item id is out of range scores 0.0 and reads nothing.  One wave per pair.  Asynchronous; n = 0 launches
+ * nothing. */
+int rk_rp3_pair_scores(int32_t n_items, int32_t n_users, int32_t k, const int32_t *nbr_id, const float *nbr_w, const int32_t *rowptr,
+                       const int32_t *col, const float *val, const int64_t *users /*[n]*/, const int64_t *items /*[n]*/, int64_t n,
+                       float *out /*[n]*/, void *stream);
+
 /* EASE victim: the linear item-item autoencoder with a closed-form fit (Steck 2019, "Embarrassingly Shallow Autoencoders for
  * Sparse Data"), repeatable to the bit.  It has no counterpart in the reference; the definition is this:
  *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending);

@@ -9,69 +9,17 @@
 #include <algorithm>
 
 #include "common.h"
+#include "item_list.h"   // the key list, its sort and the band search, shared with rp3beta.hip
 
-typedef unsigned long long ik_key;
-
-static constexpr int kIkThreads = 256;
-static constexpr int kIkKeys = 512;                             // ik_key buf[512]: [0, 128) running list | [128, 384) pending | [384, 512) zeros
-static constexpr int kIkPending = 256;                          // one chunk of candidates (one per thread) always fits an empty pending area
-static constexpr int kIkMiscBytes = 64;
-// LDS of one neighbour workgroup: ik_key buf[kIkKeys] | uint32 misc[16] | int32 acc[band]; every offset a multiple of 16
-static constexpr int kIkNbrScratchBytes = 8 * kIkKeys + kIkMiscBytes;
 static_assert(4 * RK_ITEMKNN_MAX_BAND + kIkNbrScratchBytes <= kLdsMaxBytes - 64, "RK_ITEMKNN_MAX_BAND does not fit a CU's LDS");
 static_assert(4 * (RK_ITEMKNN_MAX_BAND + 64) + kIkNbrScratchBytes > kLdsMaxBytes - 64, "RK_ITEMKNN_MAX_BAND is not the largest band");
-static_assert(RK_ITEMKNN_MAX_BAND % 64 == 0 && RK_KNN_MAX_K == 128 && kIkPending == kIkThreads, "the list layout is written for 128 slots");
-// a row longer than this is binary-searched for the band's segment; a shorter one is strided whole and filtered (two dependent
-// searches cost more than two strides of the row)
-static constexpr int kIkSearchFrom = 128;
+static_assert(RK_ITEMKNN_MAX_BAND % 64 == 0, "bands are multiples of 64");
 static constexpr int kIkAutoBand = 8192;                        // automatic band: 36 KiB per workgroup, 4 workgroups per CU
 // the scoring kernel's LDS holds byte rows only (no scratch), each padded to 16 bytes
 static constexpr int kIkScoreLdsBytes = kLdsMaxBytes - 64;
 static_assert(RK_ITEMKNN_MAX_ITEMS % 16 == 0 && RK_ITEMKNN_MAX_ITEMS <= kIkScoreLdsBytes && RK_ITEMKNN_MAX_ITEMS + 16 > kIkScoreLdsBytes,
               "RK_ITEMKNN_MAX_ITEMS is the largest catalogue whose single byte row fits a CU's LDS");
 static_assert(RK_ITEMKNN_MAX_USER_BLOCK == 16, "the scoring kernel is instantiated for 1, 2, 4, 8 and 16 accumulators");
-
-// first index in the ascending col[b, e) whose item is >= x
-__device__ __forceinline__ int ik_lower_bound(const int *__restrict__ col, int b, int e, int x)
-{
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        if (col[mid] < x) b = mid + 1; else e = mid;
-    }
-    return b;
-}
-
-// How many threads of the block pass `pred`; every thread gets the count.  One barrier: the four per-wave counts alternate
-// between two sets of slots, so a wave that runs ahead into the next call writes the other set.  (__syncthreads_count would
-// bring a static LDS variable, and the largest band leaves no room for one.)
-__device__ __forceinline__ int ik_block_count(bool pred, unsigned *slots, int &phase)
-{
-    const unsigned long long m = __ballot(pred);
-    unsigned *s = slots + 4 * (phase & 1);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = (unsigned)__popcll(m);
-    __syncthreads();
-    phase ^= 1;
-    return (int)((s[0] + s[1]) + (s[2] + s[3]));
-}
-
-// descending bitonic sort of buf[0, 512), one compare-exchange per thread and step.  All threads of the block call it; it
-// begins and ends with a barrier.
-__device__ void ik_sort(ik_key *buf)
-{
-    const int tid = threadIdx.x;
-    __syncthreads();
-#pragma unroll 1
-    for (int size = 2; size <= kIkKeys; size <<= 1) {
-#pragma unroll 1
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            const int pos = (tid / stride) * 2 * stride + (tid % stride), j = pos + stride;
-            const ik_key a = buf[pos], b = buf[j];
-            const bool desc = (pos & size) == 0;
-            if ((a < b) == desc && a != b) { buf[pos] = b; buf[j] = a; }
-            __syncthreads();
-        }
-    }
-}
 
 __global__ __launch_bounds__(kIkThreads) void itemknn_neighbors_kernel(int n_users, int n_items, const int *__restrict__ rowptr,
                                                                        const int *__restrict__ col, const float *__restrict__ val,

@@ -43,6 +43,9 @@ MODEL = {
         # seed None = the initialisation's and the device RNG's seed is drawn from torch's global RNG at .I()
         "multvae": {"hidden_dim": 600, "latent_dim": 200, "dropout": 0.5, "anneal_cap": 0.2, "total_anneal_steps": 200000,
                     "batch_size": 500, "optim": "adam", "lr": 1e-3, "seed": None},
+        # build-specific (no reference counterpart): the random-walk item-item recommender (P3alpha, Cooper et al. 2014; RP3beta,
+        # Christoffel et al. 2015), victim/rp3beta.py; beta = 0 is P3alpha; band None = automatic
+        "rp3beta": {"alpha": 1.0, "beta": 0.6, "k": 100, "band": None},
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},

@@ -7,6 +7,7 @@ from .lightgcn import LightGCN
 from .mf import MF
 from .multvae import MultVAE
 from .ncf import NCF
+from .rp3beta import RP3beta
 from .slim import SLIM
 
-__all__ = ["APR", "BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "MultVAE", "NCF", "SLIM"]
+__all__ = ["APR", "BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "MultVAE", "NCF", "RP3beta", "SLIM"]
