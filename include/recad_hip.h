@@ -348,7 +348,12 @@ int rk_adam_step_dev(int64_t n, float *param, const float *grad, float *m, float
  * in); items in the user's seen list (CSR seen_ptr/seen_idx indexed by user_ids[b], ids sorted ascending)
  * are excluded (normal.py:133-143).  Outputs per user: top_ids/top_scores[K] sorted by (score desc, item id
  * asc), padded with -1/-inf; for each target t its score and rank among the unseen items (hit@k <=> rank < k).
- * Two paths, identical results (ids, scores, target scores and ranks bit for bit):
+ * Scores are ranked by one key (score_panel.h score_key): -0.0 ties with +0.0, -inf and negative NaNs are in no list and count in
+ * no rank, a positive NaN ranks above +inf.  The panel path requires finite tables: it compares scores as floats, so a positive
+ * NaN score is in none of its lists and counts in none of its ranks; scores that overflow to +-inf from finite tables are ranked
+ * alike on both paths.  A caller that cannot vouch for its tables asks for RK_SCORE_GEMM (recad_amd.evaluate checks them once per
+ * evaluation when the plan took the panel path).
+ * Two paths, identical results on finite tables (ids, scores, target scores and ranks bit for bit):
  *   RK_SCORE_GEMM  -- GEMM into a [nb, n_items] matrix (row stride plan.ld_scores) in `scratch` + a selection pass: small user blocks, catalogues of < 16 384
  *                     items, and everything the panel form does not take;
  *   RK_SCORE_PANEL -- the register-resident panel form, recad_amd/csrc/score_panel.h: a workgroup holds the scores of 16 / 32

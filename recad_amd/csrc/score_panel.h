@@ -330,7 +330,10 @@ __global__ __launch_bounds__(kPanNT, RB == 1 ? 4 : 2) void score_panel_kernel(co
     };
     // target scores before masking (normal.py:83-85): one extra MFMA tile whose "items" are the targets -- the same k-ordered
     // chain as every other score; every wave computes it (no LDS hand-off), lanes 0..15 of wave 0 write it out
-    float ts[RB][NTG], ub[RB];
+    // tsge: the target score for the `>=` / `==` compares -- ts itself, except -FLT_MAX for a target that scores -inf: such a target
+    // ranks behind every rankable item and ties with none, so an unseen -inf item in front of it is not counted (a float
+    // compare against -inf would count it; the selection kernels' key 0 is not rankable).  x >= -FLT_MAX <=> x > -inf.
+    float ts[RB][NTG], tsge[RB][NTG], ub[RB];
     int tgt[NTG], cntr[RB][NTG];
 #pragma unroll
     for (int t = 0; t < NTG; ++t) tgt[t] = t < n_in ? a.targets[t] : -1;
@@ -358,6 +361,7 @@ __global__ __launch_bounds__(kPanNT, RB == 1 ? 4 : 2) void score_panel_kernel(co
             if (a.ubias && t < n_in) v = ((v + ub[rb]) + a.ibias[tgt[t]]) + a.mean;
             if (w == 0 && g == 0 && t < n_in && my_uid >= 0) a.target_score[(size_t)(row0 + rb * 16 + u) * a.n_targets + t] = v;
             ts[rb][t] = __shfl(v, u, 64);
+            tsge[rb][t] = ts[rb][t] == -INFINITY ? -FLT_MAX : ts[rb][t];
             cntr[rb][t] = 0;
         }
     }
@@ -532,7 +536,7 @@ __global__ __launch_bounds__(kPanNT, RB == 1 ? 4 : 2) void score_panel_kernel(co
                     for (int i = 0; i < NTW; ++i) {
                         if (TM == 1) {
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) cntr[rb][0] += acc[rb][i][r] >= ts[rb][0] ? 1 : 0;
+                            for (int r = 0; r < 4; ++r) cntr[rb][0] += acc[rb][i][r] >= tsge[rb][0] ? 1 : 0;
                         } else if (TM == 2) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) cntr[rb][0] += acc[rb][i][r] > ts[rb][0] ? 1 : 0;
@@ -543,14 +547,14 @@ __global__ __launch_bounds__(kPanNT, RB == 1 ? 4 : 2) void score_panel_kernel(co
                                 const int tile0 = pbase + 16 * (w + 8 * i);       // wave-uniform
                                 if (tile0 + 16 <= tgt[t]) {
 #pragma unroll
-                                    for (int r = 0; r < 4; ++r) cntr[rb][t] += acc[rb][i][r] >= ts[rb][t] ? 1 : 0;
+                                    for (int r = 0; r < 4; ++r) cntr[rb][t] += acc[rb][i][r] >= tsge[rb][t] ? 1 : 0;
                                 } else if (tile0 > tgt[t]) {
 #pragma unroll
                                     for (int r = 0; r < 4; ++r) cntr[rb][t] += acc[rb][i][r] > ts[rb][t] ? 1 : 0;
                                 } else {
 #pragma unroll
                                     for (int r = 0; r < 4; ++r)
-                                        cntr[rb][t] += (id0 + r != tgt[t] && (acc[rb][i][r] > ts[rb][t] || (acc[rb][i][r] == ts[rb][t] && id0 + r < tgt[t]))) ? 1 : 0;
+                                        cntr[rb][t] += (id0 + r != tgt[t] && (acc[rb][i][r] > ts[rb][t] || (acc[rb][i][r] == tsge[rb][t] && id0 + r < tgt[t]))) ? 1 : 0;
                                 }
                             }
                         }
@@ -820,9 +824,11 @@ __global__ __launch_bounds__(kPanNT, RB == 1 ? 4 : 2) void score_panel_kernel(co
                         if (!counted && !masked) {
 #pragma unroll
                             for (int q = 0; q < NTG; ++q)
-                                cntr[rb][q] += (id0 + r != tgt[q] && (sc > ts[rb][q] || (sc == ts[rb][q] && id0 + r < tgt[q]))) ? 1 : 0;
+                                cntr[rb][q] += (id0 + r != tgt[q] && (sc > ts[rb][q] || (sc == tsge[rb][q] && id0 + r < tgt[q]))) ? 1 : 0;
                         }
-                        if (!masked && (!strict || sc > tau)) {
+                        // (sc > -inf: an unrankable score -- -inf, key 0 -- is in no list, like in the fast form, whose bound never falls
+                        //  below -FLT_MAX.  Without it a row with fewer than K rankable items listed the item, its score key_score(0))
+                        if (!masked && sc > -INFINITY && (!strict || sc > tau)) {
                             const int slot = atomicAdd(&sCnt[row], 1);
                             sList[row * kPanCap + slot] = pan_raw(sc, (unsigned)(id0 + r));
                         }

@@ -29,6 +29,23 @@ def score_plan(nb, n_items, dim, K, n_targets, request=None):
     return out
 
 
+def tables_finite(*tabs):
+    """True when every scoring table (tensor, float or None) is finite.  One reduction per table and ONE read-back: the panel path
+    of rk_score_topk requires finite tables (include/recad_hip.h), so a plan that took it is checked once per evaluation and a
+    table with a NaN or an infinity goes through RK_SCORE_GEMM, whose selection ranks keys."""
+    ok = None
+    for t in tabs:
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            if not np.isfinite(float(t)):
+                return False
+            continue
+        f = torch.isfinite(t).all()
+        ok = f if ok is None else ok & f
+    return True if ok is None else bool(ok)
+
+
 # what full_catalog_topk asks the library for when its caller does not say: None = the library's choice.  The GPU tests and the
 # probes set it (tests/conftest-style fixtures) -- the library itself reads no environment variable for this any more.
 SCORE_REQUEST = None
@@ -41,7 +58,9 @@ def full_catalog_topk(victim, user_ids, seen_ptr, seen_idx, targets, K=100, chun
     within a user (dataset.train_csr_sorted()): the fused sweep walks each list with a cursor.  Host arrays are
     checked and sorted here when needed; device tensors are taken as sorted.
     Returns dict of arrays top_ids[n,K], top_scores[n,K], target_score[n,T], target_rank[n,T]: host numpy
-    arrays, or (to_host=False) device tensors left in HBM, no synchronisation.
+    arrays, or (to_host=False) device tensors left in HBM, no synchronisation -- except when the plan takes the panel path, which
+    requires finite tables (include/recad_hip.h): the tables are then checked first, one reduction and ONE read-back per call
+    (tables_finite; its cost next to a panel sweep has not been measured), and tables that are not finite go through the GEMM path.
     """
     _lib.require_gpu()
     if request is None:
@@ -82,6 +101,9 @@ def full_catalog_topk(victim, user_ids, seen_ptr, seen_idx, targets, K=100, chun
         # takes the panel form, its scratch does not grow with the block, so everything goes in ONE call; the GEMM + selection
         # path works through blocks of `chunk` users (its scratch is the block's score matrix)
         plan = score_plan(n, n_items, d, K, T, request)
+        if plan.path == _lib.RK_SCORE_PANEL and not tables_finite(utab, itab, ubias, ibias, mean):
+            request = {"path": "gemm"}      # the panel path requires finite tables (recad_hip.h): a diverged victim is ranked by keys
+            plan = score_plan(n, n_items, d, K, T, request)
         if plan.path != _lib.RK_SCORE_PANEL:
             plan = score_plan(chunk, n_items, d, K, T, request)
         else:
@@ -120,6 +142,16 @@ class EvalSession:
     evaluation costs one enqueue instead of a Python loop (the perturb-retrain loops that re-score a victim after every
     epoch, bench.py's scorings / s).  Results are device tensors owned by the session, overwritten by the next run().
 
+    A plan that takes the panel path requires finite tables (include/recad_hip.h), so EVERY run() of such a plan first asks
+    _panel_ok(), in front of the launch or the replay and outside the captured region: one reduction per table and one read-back
+    (a host synchronisation whose cost next to a panel sweep has not been measured).  Tables are trained in place between runs --
+    also by the library's own Adam, through raw pointers that move no version counter -- so nothing is cached.  Victims with
+    static tables (MF) have the tables themselves checked; victims whose tables come out of a propagation (LightGCN) have the
+    propagation's INPUTS checked, their parameters.  That rests on an assumption: the propagation is a normalised average
+    (weights in (0, 1], a mean over the layers), which keeps finite inputs finite unless they lie within a factor of the largest
+    degree of FLT_MAX; such parameters are not caught.  Not finite: the same evaluation through the GEMM path, with a graph of
+    its own.
+
     The graph holds the victim's table / workspace pointers: it is re-captured when the victim's native handle changes
     (new graph, new dimension), and never used for victims without scoring_tables() (NCF: score_matrix) or with a
     host-synchronising propagation (fuse_layers)."""
@@ -155,6 +187,7 @@ class EvalSession:
         if chunk is None:
             chunk = max(256, min(8192, (1 << 31) // max(n_items, 1)))
         chunk = max(1, min(int(chunk), max(n, 1)))
+        self._gemm_chunk, self._gemm = chunk, None      # (the fallback of a panel plan whose tables are not finite: made when first needed)
         plan = score_plan(max(n, 1), n_items, d, self.K, T, self.request)
         if plan.path != _lib.RK_SCORE_PANEL:
             plan = score_plan(chunk, n_items, d, self.K, T, self.request)
@@ -201,20 +234,35 @@ class EvalSession:
             self._static_tabs, self._static_key = tabs, key
             self._graph, self._graph_key = None, None     # the captured pointers / mean are stale: direct launches, re-capture
 
-    def _launch(self):
+    def _panel_ok(self):
+        """Panel plans only: are the tables the plan is about to score finite?  (class docstring)"""
+        if self._static:      # (on every run: in-place training moves no key)
+            return tables_finite(*self._static_tabs)
+        params = getattr(self.victim, "parameters", None)
+        if params is None:        # no parameters to ask: the tables themselves (LightGCN-like victims: one more propagation)
+            return tables_finite(*self.victim.scoring_tables())
+        return tables_finite(*[p.detach() for p in params()])
+
+    def _launch(self, use_gemm=False):
         v, L, plan = self.victim, _lib.lib(), self.plan
         utab, itab, ubias, ibias, mean = self._static_tabs if self._static_tabs is not None else v.scoring_tables()   # (LightGCN: the propagation's launches)
         utab, itab = utab.contiguous(), itab.contiguous()
         if ubias is not None:
             ubias, ibias = ubias.contiguous().view(-1), ibias.contiguous().view(-1)
         n_items, d = itab.shape
+        chunk, scratch = self.chunk, self.scratch
+        if use_gemm:
+            if self._gemm is None:
+                gplan = score_plan(self._gemm_chunk, n_items, d, self.K, self.T, {"path": "gemm"})
+                self._gemm = (gplan, torch.empty(int(gplan.scratch_floats), dtype=torch.float32, device=self.dev))
+            (plan, scratch), chunk = self._gemm, self._gemm_chunk
         st = _lib.stream_ptr()
-        for s in range(0, self.n, self.chunk):
-            e = min(self.n, s + self.chunk)
+        for s in range(0, self.n, chunk):
+            e = min(self.n, s + chunk)
             _lib.check(L.rk_score_topk(
                 d, _lib.ptr(utab), e - s, _lib.ptr(self.users[s:e]), _lib.ptr(itab), n_items, _lib.ptr(ubias), _lib.ptr(ibias), float(mean),
                 _lib.ptr(self.seen_ptr), _lib.ptr(self.seen_idx), self.K, _lib.ptr(self.top_ids[s:e]), _lib.ptr(self.top_scores[s:e]),
-                _lib.ptr(self.targets), self.T, _lib.ptr(self.tscore[s:e]), _lib.ptr(self.trank[s:e]), C.byref(plan), _lib.ptr(self.scratch), st),
+                _lib.ptr(self.targets), self.T, _lib.ptr(self.tscore[s:e]), _lib.ptr(self.trank[s:e]), C.byref(plan), _lib.ptr(scratch), st),
                 "rk_score_topk")
         if self.T and self.n:
             _lib.check(L.rk_hit_counts(_lib.ptr(self.trank), self.n, self.T, _lib.ptr(self.ks), len(self.topks), _lib.ptr(self.counts), st), "rk_hit_counts")
@@ -226,14 +274,16 @@ class EvalSession:
 
     def run(self):
         """-> dict of device tensors (top_ids [n, K], top_scores, target_score [n, T], target_rank, hit_counts [T, len(topks)], and
-        with quality= the sums quality_out [1 + 5 len(topks)] of rk_rank_metrics); no synchronisation."""
+        with quality= the sums quality_out [1 + 5 len(topks)] of rk_rank_metrics); no synchronisation, but for the table check of a plan
+        that takes the panel path (class docstring)."""
         self._runs += 1
         self._refresh_static()
-        key = (getattr(self.victim, "_handle_key", None), self._static_key)
+        use_gemm = self.plan.path == _lib.RK_SCORE_PANEL and not self._panel_ok()
+        key = (getattr(self.victim, "_handle_key", None), self._static_key, use_gemm)
         if self.want_graph and self._graph is not None and self._graph_key == key:
             self._graph.replay()
         else:
-            self._launch()
+            self._launch(use_gemm)
             if self.want_graph and self._runs >= 2 and (self._graph is None or self._graph_key != key):
                 # capture on the SECOND run (a single evaluation never pays for a capture; handles, plans and lazily built
                 # schedules exist by now); a failed capture keeps the eager path
@@ -241,8 +291,8 @@ class EvalSession:
                     torch.cuda.synchronize()
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g):
-                        self._launch()
-                    self._graph, self._graph_key = g, (getattr(self.victim, "_handle_key", None), self._static_key)
+                        self._launch(use_gemm)
+                    self._graph, self._graph_key = g, (getattr(self.victim, "_handle_key", None), self._static_key, use_gemm)
                     self._graph.replay()     # (the capture itself ran nothing: results must come from an execution)
                 except Exception as exc:    # noqa: BLE001
                     import warnings
