@@ -88,6 +88,16 @@ __device__ __forceinline__ int rk_find_sorted(const int *__restrict__ col, int b
     return -1;
 }
 
+// first index in the ascending entries [b, e) of col whose value is >= x (e when there is none)
+__device__ __forceinline__ int rk_lower_bound(const int *__restrict__ col, int b, int e, int x)
+{
+    while (b < e) {
+        const int mid = (b + e) >> 1;
+        if (col[mid] < x) b = mid + 1; else e = mid;
+    }
+    return b;
+}
+
 // Stream-ordered scratch of one entry point.  get() is hipMallocAsync on the stream; the destructor hands every buffer
 // back with hipFreeAsync on the same stream (errors ignored there), so each early return of RK_HIP / RK_CHECK_LAUNCH
 // frees what was allocated before it.

@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "item_list.h"   // kIkSearchFrom: the gram kernel walks as the neighbour kernels do
 
 typedef float ea_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -18,20 +19,10 @@ static constexpr int kEaThreads = 256;
 static constexpr int kEaTile = 64;                              // edge of a panel / trailing tile: four waves, 32 x 32 each
 static constexpr int kEaLd = kEaTile + 1;                       // odd leading dimension: rows and columns of a tile are conflict-free
 static constexpr int kEaGramBand = 8192;                        // int32 accumulators of one gram workgroup (32 KiB)
-static constexpr int kEaSearchFrom = 128;                       // as kIkSearchFrom of itemknn.hip
 static_assert(RK_EASE_BLOCK_LARGE == kEaTile && RK_EASE_BLOCK_SMALL == 32, "a pivot block is at most one tile wide");
 static_assert((long long)RK_EASE_MAX_ITEMS / kEaTile <= 65535, "the trailing grid's y dimension");
 
 // ---- gram
-__device__ __forceinline__ int ea_lower_bound(const int *__restrict__ col, int b, int e, int x)
-{
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        if (col[mid] < x) b = mid + 1; else e = mid;
-    }
-    return b;
-}
-
 __global__ void ease_status_kernel(int *status, int rule, int index)
 {
     status[0] = rule;
@@ -80,9 +71,9 @@ __global__ __launch_bounds__(kEaThreads) void ease_gram_kernel(int n_users, int 
             if (u < 0 || u >= n_users) continue;
             const int q = (int)cval[e];
             int s0 = rowptr[u], s1 = rowptr[u + 1];
-            if (!whole && s1 - s0 > kEaSearchFrom) {
-                s0 = ea_lower_bound(col, s0, s1, lo);
-                s1 = ea_lower_bound(col, s0, s1, lo + bn);
+            if (!whole && s1 - s0 > kIkSearchFrom) {
+                s0 = rk_lower_bound(col, s0, s1, lo);
+                s1 = rk_lower_bound(col, s0, s1, lo + bn);
             }
             for (int p = s0 + lane; p < s1; p += 64) {
                 const int j = col[p] - lo;

@@ -1,6 +1,8 @@
 // The neighbour-list machinery of the item-item fits (itemknn.hip, rp3beta.hip): one 256-thread workgroup per item keeps a
 // running list of the largest 64-bit keys (bits of w) << 32 | (0xFFFFFFFF - j) -- all distinct, descending key = (w descending,
-// j ascending) -- merged across bands of candidates through a pending area and a bitonic sort, plus the band search of a row.
+// j ascending) -- merged across bands of candidates through a pending area and a bitonic sort.  Beside it what the item-item
+// files share: the band refusal and automatic band, the score term, and the row length from which a band segment is searched
+// (ease.hip's Gram kernel walks by it too).
 #pragma once
 #include "common.h"
 
@@ -17,14 +19,24 @@ static_assert(RK_KNN_MAX_K == 128 && kIkPending == kIkThreads, "the list layout 
 // searches cost more than two strides of the row)
 static constexpr int kIkSearchFrom = 128;
 
-// first index in the ascending col[b, e) whose item is >= x
-__device__ __forceinline__ int ik_lower_bound(const int *__restrict__ col, int b, int e, int x)
+// the automatic band (band == 0: the catalogue in equal bands of at most auto_band, rounded up to 64) or the refusal of a bad one
+static inline int ik_resolve_band(const char *who, int *band, int max_band, int auto_band, int n_items)
 {
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        if (col[mid] < x) b = mid + 1; else e = mid;
+    if (*band != 0 && (*band < 64 || *band > max_band || *band % 64))
+        RK_FAIL(RK_EINVAL, "%s: band = %d (0, or a multiple of 64 in 64..%d)", who, *band, max_band);
+    if (*band == 0) {
+        const int n_bands = (n_items + auto_band - 1) / auto_band;
+        *band = (((n_items + n_bands - 1) / n_bands) + 63) / 64 * 64;
     }
-    return b;
+    return RK_OK;
+}
+
+// s + fl(w * q): two roundings, never one fused multiply-add
+__device__ __forceinline__ float ik_add_term(float s, float w, float q)
+{
+#pragma clang fp contract(off)
+    const float term = w * q;
+    return s + term;
 }
 
 // How many threads of the block pass `pred`; every thread gets the count.  One barrier: the four per-wave counts alternate

@@ -9,7 +9,7 @@
 #include <algorithm>
 
 #include "common.h"
-#include "item_list.h"   // the key list, its sort and the band search, shared with rp3beta.hip
+#include "item_list.h"   // the key list, its sort and the band constants, shared with rp3beta.hip
 
 static_assert(4 * RK_ITEMKNN_MAX_BAND + kIkNbrScratchBytes <= kLdsMaxBytes - 64, "RK_ITEMKNN_MAX_BAND does not fit a CU's LDS");
 static_assert(4 * (RK_ITEMKNN_MAX_BAND + 64) + kIkNbrScratchBytes > kLdsMaxBytes - 64, "RK_ITEMKNN_MAX_BAND is not the largest band");
@@ -57,8 +57,8 @@ __global__ __launch_bounds__(kIkThreads) void itemknn_neighbors_kernel(int n_use
                 const int q = (int)cval[e];
                 int s0 = rowptr[u], s1 = rowptr[u + 1];
                 if (!whole && s1 - s0 > kIkSearchFrom) {
-                    s0 = ik_lower_bound(col, s0, s1, lo);
-                    s1 = ik_lower_bound(col, s0, s1, lo + bn);
+                    s0 = rk_lower_bound(col, s0, s1, lo);
+                    s1 = rk_lower_bound(col, s0, s1, lo + bn);
                 }
                 for (int p = s0 + lane; p < s1; p += 64) {
                     const int j = col[p] - lo;
@@ -116,12 +116,7 @@ RK_EXPORT int rk_itemknn_neighbors(int32_t n_users, int32_t n_items, const int32
     if (n_users <= 0 || n_items <= 0 || !rowptr || !col || !val || !colptr || !crow || !cval || !rnorm_item || !nbr_id || !nbr_w)
         RK_FAIL(RK_EINVAL, "rk_itemknn_neighbors: bad arguments");
     if (k < 1 || k > RK_KNN_MAX_K) RK_FAIL(RK_EINVAL, "rk_itemknn_neighbors: k = %d outside 1..%d", k, RK_KNN_MAX_K);
-    if (band != 0 && (band < 64 || band > RK_ITEMKNN_MAX_BAND || band % 64))
-        RK_FAIL(RK_EINVAL, "rk_itemknn_neighbors: band = %d (0, or a multiple of 64 in 64..%d)", band, RK_ITEMKNN_MAX_BAND);
-    if (band == 0) {
-        const int n_bands = (n_items + kIkAutoBand - 1) / kIkAutoBand;
-        band = (((n_items + n_bands - 1) / n_bands) + 63) / 64 * 64;
-    }
+    if (int rc = ik_resolve_band("rk_itemknn_neighbors", &band, RK_ITEMKNN_MAX_BAND, kIkAutoBand, n_items)) return rc;
     static RkPerDeviceOnce attr_once;
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
@@ -137,14 +132,6 @@ RK_EXPORT int rk_itemknn_neighbors(int32_t n_users, int32_t n_items, const int32
 }
 
 // ---- scores
-// s + fl(w * q): two roundings, never one fused multiply-add
-__device__ __forceinline__ float ik_add_term(float s, float w, float q)
-{
-#pragma clang fp contract(off)
-    const float term = w * q;
-    return s + term;
-}
-
 // Block x of the grid stages users [x * ub, x * ub + ub) of user_ids as byte rows; block y walks items [y * seg, y * seg + seg).
 // A lane owns an item: slot t of 64 consecutive items is one coalesced line of each table, read once for the ub users.
 template <int UB>

@@ -89,16 +89,6 @@ RK_EXPORT int rk_knn_norms(int32_t n_users, int32_t n_items, const int32_t *rowp
 }
 
 // ---- DegSim
-// first index in the ascending crow[b, e) whose user is >= x
-__device__ __forceinline__ int knn_lower_bound(const int *__restrict__ crow, int b, int e, int x)
-{
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        if (crow[mid] < x) b = mid + 1; else e = mid;
-    }
-    return b;
-}
-
 // The kk-th largest bit pattern T among the nonzero words >= floor_ of acc[0, n_acc) and top[0, kk), by three radix digits
 // (bits 29..19, 18..8, 7..0: every w is below 2, so bits 31 and 30 are clear), then top[0, kk) = the words above T and as
 // many copies of T as it takes.  Fewer than kk such words: T = 0 and the list is padded with zeros.  Returns T (the next
@@ -205,8 +195,8 @@ __global__ __launch_bounds__(kKnnThreads) void knn_degsim_kernel(int n_users, in
                 const int q = (int)val[e];
                 int s0 = colptr[i], s1 = colptr[i + 1];
                 if (!whole) {
-                    s0 = knn_lower_bound(crow, s0, s1, lo);
-                    s1 = knn_lower_bound(crow, s0, s1, lo + bn);
+                    s0 = rk_lower_bound(crow, s0, s1, lo);
+                    s1 = rk_lower_bound(crow, s0, s1, lo + bn);
                 }
                 for (int p = s0 + lane; p < s1; p += 64) {
                     const int v = crow[p] - lo;

@@ -131,8 +131,8 @@ __global__ __launch_bounds__(kIkThreads) void rp3_neighbors_kernel(int n_users, 
                 if (u < 0 || u >= n_users) continue;
                 int s0 = rowptr[u], s1 = rowptr[u + 1];
                 if (!whole && s1 - s0 > kIkSearchFrom) {
-                    s0 = ik_lower_bound(col, s0, s1, lo);
-                    s1 = ik_lower_bound(col, s0, s1, lo + bn);
+                    s0 = rk_lower_bound(col, s0, s1, lo);
+                    s1 = rk_lower_bound(col, s0, s1, lo + bn);
                 }
                 for (int p = s0 + lane; p < s1; p += 64) {
                     const int j = col[p] - lo;
@@ -192,12 +192,7 @@ RK_EXPORT int rk_rp3_neighbors(int32_t n_users, int32_t n_items, const int32_t *
     if (n_users >= RK_RP3_MAX_USERS)
         RK_FAIL(RK_EINVAL, "rk_rp3_neighbors: %d users, fewer than %d keep every dot below 2^63", n_users, RK_RP3_MAX_USERS);
     if (k < 1 || k > RK_KNN_MAX_K) RK_FAIL(RK_EINVAL, "rk_rp3_neighbors: k = %d outside 1..%d", k, RK_KNN_MAX_K);
-    if (band != 0 && (band < 64 || band > RK_RP3_MAX_BAND || band % 64))
-        RK_FAIL(RK_EINVAL, "rk_rp3_neighbors: band = %d (0, or a multiple of 64 in 64..%d)", band, RK_RP3_MAX_BAND);
-    if (band == 0) {
-        const int n_bands = (n_items + kRpAutoBand - 1) / kRpAutoBand;
-        band = (((n_items + n_bands - 1) / n_bands) + 63) / 64 * 64;
-    }
+    if (int rc = ik_resolve_band("rk_rp3_neighbors", &band, RK_RP3_MAX_BAND, kRpAutoBand, n_items)) return rc;
     static RkPerDeviceOnce attr_once;
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
@@ -213,14 +208,6 @@ RK_EXPORT int rk_rp3_neighbors(int32_t n_users, int32_t n_items, const int32_t *
 }
 
 // ---- scores
-// s + fl(w * q): two roundings, never one fused multiply-add
-__device__ __forceinline__ float rp_add_term(float s, float w, float q)
-{
-#pragma clang fp contract(off)
-    const float term = w * q;
-    return s + term;
-}
-
 // One single-wave workgroup per entry of user_ids.  Per band of columns the fp32 row sits in LDS; the wave takes the user's items
 // 64 at a time into its lanes and walks them in ascending order, the (at most 128) slots of an item's list across the lanes in
 // two trips.  The ids of one list are distinct, so the lanes of one trip never meet; LDS operations of a wave complete in program
@@ -271,8 +258,8 @@ __global__ __launch_bounds__(64) void rp3_scores_kernel(int n_users, int n_items
                     }
                 }
                 // id - lo of an unused slot (-1) is negative: outside the band like any other column of another band
-                if ((unsigned)a0 < (unsigned)bn) rp_row[a0] = rp_add_term(rp_row[a0], v0, q);
-                if ((unsigned)a1 < (unsigned)bn) rp_row[a1] = rp_add_term(rp_row[a1], v1, q);
+                if ((unsigned)a0 < (unsigned)bn) rp_row[a0] = ik_add_term(rp_row[a0], v0, q);
+                if ((unsigned)a1 < (unsigned)bn) rp_row[a1] = ik_add_term(rp_row[a1], v1, q);
                 __builtin_amdgcn_wave_barrier();
             }
         }
@@ -289,13 +276,8 @@ RK_EXPORT int rk_rp3_scores(int32_t n_users, int32_t n_items, int32_t k, const i
     if (n_users <= 0 || n_items <= 0 || nb < 0 || !nbr_id || !nbr_w || !rowptr || !col || !val || !user_ids || !out)
         RK_FAIL(RK_EINVAL, "rk_rp3_scores: bad arguments");
     if (k < 1 || k > RK_KNN_MAX_K) RK_FAIL(RK_EINVAL, "rk_rp3_scores: k = %d outside 1..%d", k, RK_KNN_MAX_K);
-    if (band != 0 && (band < 64 || band > RK_RP3_MAX_BAND || band % 64))
-        RK_FAIL(RK_EINVAL, "rk_rp3_scores: band = %d (0, or a multiple of 64 in 64..%d)", band, RK_RP3_MAX_BAND);
-    if (nb == 0) return RK_OK;
-    if (band == 0) {
-        const int n_bands = (n_items + kRpAutoScoreBand - 1) / kRpAutoScoreBand;
-        band = (((n_items + n_bands - 1) / n_bands) + 63) / 64 * 64;
-    }
+    if (int rc = ik_resolve_band("rk_rp3_scores", &band, RK_RP3_MAX_BAND, kRpAutoScoreBand, n_items)) return rc;
+    if (nb == 0) return RK_OK;                                         // after the refusal of a bad band, as before
     static RkPerDeviceOnce attr_once;
     int attr_dev;
     if (attr_once.need(&attr_dev)) {
@@ -343,7 +325,7 @@ __global__ __launch_bounds__(256) void rp3_pair_kernel(int n_items, int n_users,
                 for (int t = lane; t < k; t += 64)
                     if (nbr_id[(size_t)t * n_items + i] == j) { w = nbr_w[(size_t)t * n_items + i]; hit = true; }
                 const unsigned long long m = __ballot(hit);
-                if (m) s = rp_add_term(s, __shfl(w, __ffsll((long long)m) - 1, 64), q);
+                if (m) s = ik_add_term(s, __shfl(w, __ffsll((long long)m) - 1, 64), q);
             }
         }
     }

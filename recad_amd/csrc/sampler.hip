@@ -11,12 +11,6 @@ __device__ __forceinline__ unsigned long long rnd(unsigned long long seed, unsig
 // uniform integer in [0, n) from 64 random bits (multiply-shift, no modulo bias to speak of)
 __device__ __forceinline__ unsigned bounded(unsigned long long r, unsigned n) { return (unsigned)(((r >> 32) * (unsigned long long)n) >> 32); }
 
-__device__ __forceinline__ int lower_bound(const int *__restrict__ a, int lo, int hi, int x)
-{
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < x) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
 // r-th (0-based) item NOT in the sorted list idx[b, e): exact, O(log deg).  idx[b+k] - k is the number of free
 // items below positive k and is non-decreasing in k, so j = #{k : idx[b+k] - k <= r} positives precede the answer.
 __device__ __forceinline__ int rth_free_item(const int *__restrict__ idx, int b, int e, int r)
@@ -42,7 +36,7 @@ __global__ void bpr_sample_kernel(int n_users, int n_items, const int *__restric
         bool ok = false;
         for (unsigned k = 2; k < 66 && !ok; ++k) {
             ng = (int)bounded(rnd(seed, (unsigned long long)t, k), (unsigned)n_items);
-            const int p = lower_bound(idx, b, e, ng);
+            const int p = rk_lower_bound(idx, b, e, ng);
             ok = !(p < e && idx[p] == ng);
         }
         if (!ok) {  // dense user: pick the r-th free item directly

@@ -32,16 +32,6 @@ struct UbaTargets {
     int users[RK_UBA_MAX_TARGETS];
 };
 
-// first index in the ascending entries [b, e) of col whose value is >= c
-__device__ __forceinline__ int lower_bound(const int *__restrict__ col, int b, int e, int c)
-{
-    while (b < e) {
-        const int mid = (b + e) >> 1;
-        if (col[mid] < c) b = mid + 1; else e = mid;
-    }
-    return b;
-}
-
 // [b, e) of side row t, clamped into [0, side_cap)
 __device__ __forceinline__ void side_row(const int *__restrict__ side_ptr, int t, int side_cap, int *b, int *e)
 {
@@ -68,7 +58,7 @@ __global__ __launch_bounds__(kBlock) void redraw_kernel(UbaTargets T, long long 
             len[tid] = -1;
             row_b[tid] = spos[tid] = 0;
         } else {
-            const int p = lower_bound(col, (int)b, (int)e, s);
+            const int p = rk_lower_bound(col, (int)b, (int)e, s);
             const bool has = p < (int)e && col[p] == s;
             len[tid] = (int)(e - b) + (has ? 0 : 1);
             row_b[tid] = (int)b;

@@ -16,9 +16,10 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._ratings import checked_norms, rating_csr, transposed
 from ..utils import get_logger
 from ..victim.base import BaseVictim
-from .pca_select_users import flag_count, rating_csr
+from .pca_select_users import flag_count
 
 SCORES = ("sync", "normality", "residual")
 SCHEDULES = ("work", "natural")
@@ -101,26 +102,15 @@ class CatchSyncSelectUsers(BaseVictim):
         U, I, rowptr, col, val = rating_csr(self.dataset, dev)
         self.user_num, self.item_num = U, I
         L, P, s = _lib.lib(), _lib.ptr, _lib.stream_ptr(dev)
-        rnorm = torch.empty(U, dtype=torch.float32, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        rc = L.rk_knn_norms(U, I, P(rowptr), P(col), P(val), P(rnorm), P(status), s)
-        if rc != 0:
-            rule, row = status.cpu().tolist()
-            if rule:       # nothing further is launched after a refusal
-                raise ValueError(f"CatchSyncSelectUsers: the rating matrix breaks rule {rule} ({_lib.RK_KNN_RULES.get(rule, '?')}), "
-                                 f"first in row {row}")
-            _lib.check(rc, "rk_knn_norms")
-        nnz = col.numel()
-        colptr = torch.empty(I + 1, dtype=torch.int32, device=dev)
-        crow = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
-        cval = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
-        _lib.check(L.rk_pca_transpose(U, I, P(rowptr), P(col), P(val), P(colptr), P(crow), P(cval), s), "rk_pca_transpose")
+        rnorm = checked_norms("CatchSyncSelectUsers", "rating matrix", U, I, rowptr, col, val)    # nothing further is launched after a refusal
+        colptr, crow, cval = transposed(U, I, rowptr, col, val)
         deg_item = torch.empty(I, dtype=torch.int32, device=dev)
         reach = torch.empty(I, dtype=torch.int32, device=dev)
         _lib.check(L.rk_cs_features(U, I, P(rowptr), P(colptr), P(crow), P(deg_item), P(reach), s), "rk_cs_features")
         cell_of = torch.empty(I, dtype=torch.int32, device=dev)
         cell_count = torch.empty(_lib.RK_CS_MAX_CELLS, dtype=torch.int32, device=dev)
         info = torch.empty(4, dtype=torch.int64, device=dev)
+        status = torch.zeros(2, dtype=torch.int32, device=dev)
         rc = L.rk_cs_cells(I, P(deg_item), P(reach), int(self.grid_bits), P(cell_of), P(cell_count), P(info), P(status), s)
         if rc != 0:
             rule, item = status.cpu().tolist()

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .._ratings import rating_csr  # noqa: F401  (callers import it from here as well)
 from ..utils import get_logger
 from ..victim.base import BaseVictim
 
@@ -58,52 +59,6 @@ def sign_fix(vecs):
     pos = np.argmax(np.abs(vecs), axis=0)
     s = np.sign(vecs[pos, np.arange(vecs.shape[1])])
     return vecs * np.where(s == 0, 1, s)
-
-
-def rating_csr(dataset, device):
-    """The defender's U x I rating matrix as a device CSR: (U, I, rowptr int32, col int32, val float32).
-    Accepts an ImplicitData (its train CSR, every value 1.0), a rating CSR tuple (ptr, idx, val[, n_items]),
-    a dense U x I array (the reference's users_mat rows), or an object whose info_describe() has "train_mat".
-    An ExplicitData gives its train rating CSR, values as they are (the reference's defense_data, explicit.py:102)."""
-    from ..dataset import ExplicitData
-
-    if isinstance(dataset, ExplicitData):
-        ptr, idx, val = dataset.rating_csr("train")
-        return (int(dataset.n_users), int(dataset.n_items), torch.as_tensor(ptr.astype(np.int32)).to(device),
-                torch.as_tensor(idx.astype(np.int32)).to(device), torch.as_tensor(val.astype(np.float32)).to(device))
-    if hasattr(dataset, "train_csr_sorted") and hasattr(dataset, "n_items"):
-        ptr, idx = dataset.train_csr_sorted()
-        U, I = int(dataset.n_users), int(dataset.n_items)
-        ptr, idx = np.asarray(ptr)[: U + 1], np.asarray(idx)[: int(ptr[U])]
-        rp = torch.as_tensor(ptr.astype(np.int32)).to(device)
-        col = torch.as_tensor(idx.astype(np.int32)).to(device)
-        return U, I, rp, col, torch.ones(col.numel(), dtype=torch.float32, device=device)
-    if hasattr(dataset, "info_describe") and not isinstance(dataset, (tuple, list)):
-        dataset = dataset.info_describe()["train_mat"]
-    if isinstance(dataset, (tuple, list)):
-        if len(dataset) not in (3, 4):
-            raise ValueError("a rating CSR is (ptr, idx, val) or (ptr, idx, val, n_items)")
-        ptr, idx, val = (torch.as_tensor(np.asarray(a) if not isinstance(a, torch.Tensor) else a) for a in dataset[:3])
-        U = int(ptr.numel()) - 1
-        I = int(dataset[3]) if len(dataset) == 4 else (int(idx.max().item()) + 1 if idx.numel() else 1)
-        if idx.numel() != int(ptr[-1].item()) or val.numel() != idx.numel():
-            raise ValueError(f"rating CSR sizes disagree: ptr[-1] = {int(ptr[-1].item())}, {idx.numel()} ids, {val.numel()} values")
-        if idx.numel() and (int(idx.min().item()) < 0 or int(idx.max().item()) >= I):
-            raise ValueError(f"rating CSR item ids outside [0, {I})")
-        if int(ptr[0].item()) != 0 or bool((ptr[1:] < ptr[:-1]).any().item()):
-            raise ValueError("rating CSR row pointers must start at 0 and not decrease")
-        return (U, I, ptr.to(device=device, dtype=torch.int32).contiguous(), idx.to(device=device, dtype=torch.int32).contiguous(),
-                val.to(device=device, dtype=torch.float32).contiguous())
-    dense = torch.as_tensor(np.asarray(dataset) if not isinstance(dataset, torch.Tensor) else dataset)
-    if dense.dim() != 2:
-        raise ValueError(f"expected a U x I rating array, got shape {tuple(dense.shape)}")
-    dense = dense.to(device=device, dtype=torch.float32)
-    U, I = dense.shape
-    mask = dense != 0
-    rp = torch.zeros(U + 1, dtype=torch.int32, device=device)
-    rp[1:] = torch.cumsum(mask.sum(dim=1), 0).to(torch.int32)
-    nz = mask.nonzero()
-    return int(U), int(I), rp, nz[:, 1].to(torch.int32).contiguous(), dense[mask].contiguous()
 
 
 class CovarianceOperator:

@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._ratings import DeviceRatings, checked_norms, transposed
 from ..utils import VarDim
 from .base import BaseVictim
 
@@ -89,28 +90,11 @@ class IALS(BaseVictim):
 
     def _ratings(self, dev):
         """The validated CSR, its transpose, and both sides' rows ordered longest first, cached per device."""
-        from ..defense.pca_select_users import rating_csr
-
         if self._csr is None or self._csr[0] != dev:
-            U, I, rowptr, col, val = rating_csr(self.dataset, dev)
-            if (U, I) != (self.num_users, self.num_items):
-                raise ValueError(f"iALS: the dataset's rating matrix is {U} x {I}, its description says {self.num_users} x {self.num_items}")
-            if col.numel() == 0:          # an empty matrix still needs addresses
-                col, val = torch.zeros(1, dtype=torch.int32, device=dev), torch.ones(1, dtype=torch.float32, device=dev)
-            L, P, s = _lib.lib(), _lib.ptr, _lib.stream_ptr(dev)
-            nnz = int(rowptr[-1].item())
-            status = torch.zeros(2, dtype=torch.int32, device=dev)
-            rnorm = torch.empty(U, dtype=torch.float32, device=dev)
-            rc = L.rk_knn_norms(U, I, P(rowptr), P(col), P(val), P(rnorm), P(status), s)                                # rules 1, 2, 3, 4
-            if rc != 0:
-                rule, row = status.cpu().tolist()
-                if not rule:
-                    _lib.check(rc, "rk_knn_norms")
-                raise ValueError(f"iALS: the rating matrix breaks rule {rule} ({_lib.RK_KNN_RULES.get(rule, '?')}), first in row {row}")
-            colptr = torch.empty(I + 1, dtype=torch.int32, device=dev)
-            crow = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
-            cval = torch.empty(max(nnz, 1), dtype=torch.float32, device=dev)
-            _lib.check(L.rk_pca_transpose(U, I, P(rowptr), P(col), P(val), P(colptr), P(crow), P(cval), s), "rk_pca_transpose")
+            U, I = self.num_users, self.num_items
+            rowptr, col, val = DeviceRatings(self.dataset, U, I, "iALS").on(dev)
+            checked_norms("iALS", "rating matrix", U, I, rowptr, col, val)              # rules 1, 2, 3, 4
+            colptr, crow, cval = transposed(U, I, rowptr, col, val)
             longest = lambda ptr: torch.argsort(ptr[1:] - ptr[:-1], descending=True, stable=True).to(torch.int32).contiguous()
             self._csr = (dev, (rowptr, col, val), (colptr, crow, cval), longest(rowptr), longest(colptr))
         return self._csr[1:]

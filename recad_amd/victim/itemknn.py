@@ -13,8 +13,8 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from ..utils import VarDim
-from .base import BaseVictim
+from .._ratings import checked_norms, transposed
+from ._fit_once import FitOnceVictim
 
 
 def check_config(k, band, user_block):
@@ -33,26 +33,19 @@ def rows_that_fit(n_items):
     return _lib.RK_ITEMKNN_MAX_ITEMS // ((int(n_items) + 15) // 16 * 16)
 
 
-class ItemKNN(BaseVictim):
+class ItemKNN(FitOnceVictim):
     victim_name = "itemknn"
+    label, state_noun = "ItemKNN", "tables"
 
     def _build(self, k, band, user_block, **config):
-        self.dataset = config["dataset"]
-        self.config = config
-        info = self.dataset.info_describe()
-        self.num_users, self.num_items = int(info["n_users"]), int(info["n_items"])
+        self._open(config)
         self.k, self.band, self.user_block = k, band, user_block
-        try:
-            check_config(k, band, user_block)
-            rows = int(k)
-        except (ValueError, TypeError):
-            rows = 0                      # the refusal is raised by the first call that would use the tables
+        # by check_config alone, not _check: a catalogue the scoring kernel cannot hold keeps its k table rows, as it always has
+        rows = int(k) if self._accepted(lambda: check_config(k, band, user_block)) else 0
         self.nbr_w = nn.Parameter(torch.zeros(rows, self.num_items, dtype=torch.float32), requires_grad=False)
         self.register_buffer("nbr_id", torch.full((rows, self.num_items), -1, dtype=torch.int32))
         self.register_buffer("fitted", torch.zeros(1, dtype=torch.int32))
-        self._csr = None                  # (device, rowptr, col, val) of the dataset's rating matrix
 
-    # ------------------------------------------------------------------ the ratings
     def _check(self):
         check_config(self.k, self.band, self.user_block)
         if self.num_items > _lib.RK_ITEMKNN_MAX_ITEMS:
@@ -61,110 +54,25 @@ class ItemKNN(BaseVictim):
             raise ValueError(f"ItemKNN: user_block = {self.user_block}, only {rows_that_fit(self.num_items)} byte rows of "
                              f"{self.num_items} items fit a CU's LDS")
 
-    def _device(self):
-        dev = self.nbr_w.device
-        if dev.type != "cuda":
-            raise _lib.HipCallError("ItemKNN tables are on the CPU: call .to('cuda') first (no CPU fallback)")
-        return dev
-
-    def _ratings(self, dev):
-        from ..defense.pca_select_users import rating_csr
-
-        if self._csr is None or self._csr[0] != dev:
-            U, I, rowptr, col, val = rating_csr(self.dataset, dev)
-            if (U, I) != (self.num_users, self.num_items):
-                raise ValueError(f"ItemKNN: the dataset's rating matrix is {U} x {I}, its description says {self.num_users} x {self.num_items}")
-            if col.numel() == 0:          # an empty matrix still needs addresses
-                col, val = torch.zeros(1, dtype=torch.int32, device=dev), torch.ones(1, dtype=torch.float32, device=dev)
-            self._csr = (dev, rowptr, col, val)
-        return self._csr[1:]
-
-    @staticmethod
-    def _norms(n_rows, n_cols, rowptr, col, val, what, dev):
-        """rk_knn_norms; a refusal raises ValueError with the rule and the row, and nothing further is launched."""
-        L, P = _lib.lib(), _lib.ptr
-        rnorm = torch.empty(n_rows, dtype=torch.float32, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        rc = L.rk_knn_norms(n_rows, n_cols, P(rowptr), P(col), P(val), P(rnorm), P(status), _lib.stream_ptr(dev))
-        if rc != 0:
-            rule, row = status.cpu().tolist()
-            if rule:
-                raise ValueError(f"ItemKNN: the {what} breaks rule {rule} ({_lib.RK_KNN_RULES.get(rule, '?')}), first in row {row}")
-            _lib.check(rc, "rk_knn_norms")
-        return rnorm
-
     # ------------------------------------------------------------------ the fit
-    def fit(self):
-        """Builds the neighbour tables from the dataset's rating matrix, whether or not they were built before."""
-        self._check()
-        dev = self._device()
-        _lib.require_gpu()
-        U, I, k = self.num_users, self.num_items, int(self.k)
-        rowptr, col, val = self._ratings(dev)
-        L, P, s = _lib.lib(), _lib.ptr, _lib.stream_ptr(dev)
-        nnz = int(col.numel())
-        colptr = torch.empty(I + 1, dtype=torch.int32, device=dev)
-        crow = torch.empty(nnz, dtype=torch.int32, device=dev)
-        cval = torch.empty(nnz, dtype=torch.float32, device=dev)
-        self._norms(U, I, rowptr, col, val, "rating matrix", dev)                       # rules 1, 2, 4 (and the user norms' rule 3)
-        _lib.check(L.rk_pca_transpose(U, I, P(rowptr), P(col), P(val), P(colptr), P(crow), P(cval), s), "rk_pca_transpose")
-        rnorm_item = self._norms(I, U, colptr, crow, cval, "transposed rating matrix (rows are items)", dev)   # r_i, rule 3
-        _lib.check(L.rk_itemknn_neighbors(U, I, P(rowptr), P(col), P(val), P(colptr), P(crow), P(cval), P(rnorm_item), k,
-                                          int(self.band or 0), None, P(self.nbr_id), P(self.nbr_w.data), s), "rk_itemknn_neighbors")
-        self.fitted.fill_(1)
-        self._known_fit = True
-        return self
-
-    _known_fit = None                     # what `fitted` holds, once it has been read back; None: not known
-
-    def _fitted_tables(self):
-        self._check()
-        dev = self._device()
-        if self._known_fit is None:
-            self._known_fit = bool(self.fitted.item())
-        if not self._known_fit:
-            self.fit()
-        return dev, self.nbr_id, self.nbr_w.data
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._known_fit = None            # `fitted` is about to be overwritten
-        return super()._load_from_state_dict(*args, **kwargs)
-
-    def train_step(self, **config):
-        """Fits on first use and is a no-op afterwards (workflow.normal_train calls it rec_epoch times).  A memory-based model
-        has no loss: the value returned is 0.0."""
-        self._fitted_tables()
-        return (0.0,)
+    def _fit(self, dev, rowptr, col, val):
+        """Builds the neighbour tables from the rating matrix."""
+        U, I = self.num_users, self.num_items
+        L, P = _lib.lib(), _lib.ptr
+        checked_norms("ItemKNN", "rating matrix", U, I, rowptr, col, val)               # rules 1, 2, 4 (and the user norms' rule 3)
+        colptr, crow, cval = transposed(U, I, rowptr, col, val)
+        rnorm_item = checked_norms("ItemKNN", "transposed rating matrix (rows are items)", I, U, colptr, crow, cval)   # r_i, rule 3
+        _lib.check(L.rk_itemknn_neighbors(U, I, P(rowptr), P(col), P(val), P(colptr), P(crow), P(cval), P(rnorm_item), int(self.k),
+                                          int(self.band or 0), None, P(self.nbr_id), P(self.nbr_w.data), _lib.stream_ptr(dev)),
+                   "rk_itemknn_neighbors")
 
     # ------------------------------------------------------------------ scoring
-    def forward(self, users, items):
-        dev, nbr_id, nbr_w = self._fitted_tables()
-        rowptr, col, val = self._ratings(dev)
-        users, items = users.long().contiguous(), items.long().contiguous()
-        out = torch.empty(users.numel(), dtype=torch.float32, device=dev)
-        _lib.check(_lib.lib().rk_itemknn_pair_scores(
-            self.num_items, self.num_users, int(self.k), _lib.ptr(nbr_id), _lib.ptr(nbr_w), _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(val),
-            _lib.ptr(users) if users.numel() else None, _lib.ptr(items) if users.numel() else None, users.numel(), _lib.ptr(out) if users.numel() else None,
-            _lib.stream_ptr(dev)), "rk_itemknn_pair_scores")
-        return out
+    def _score_pairs(self, csr, users, items, n, out, stream):
+        P = _lib.ptr
+        _lib.check(_lib.lib().rk_itemknn_pair_scores(self.num_items, self.num_users, int(self.k), P(self.nbr_id), P(self.nbr_w.data),
+                                                     *map(P, csr), users, items, n, out, stream), "rk_itemknn_pair_scores")
 
-    def score_matrix(self, user_ids, out):
-        """out[len(user_ids), n_items] <- the score of every item for each user (int32 ids on the device), seen items included;
-        the batched evaluation then runs rk_topk_rows on it."""
-        dev, nbr_id, nbr_w = self._fitted_tables()
-        rowptr, col, val = self._ratings(dev)
-        _lib.check(_lib.lib().rk_itemknn_scores(
-            self.num_items, int(self.k), _lib.ptr(nbr_id), _lib.ptr(nbr_w), _lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(val),
-            user_ids.numel(), _lib.ptr(user_ids), int(self.user_block or 0), _lib.ptr(out), _lib.stream_ptr(dev)), "rk_itemknn_scores")
-
-    def input_describe(self):
-        return {
-            "train_step": {},
-            "forward": {"users": (torch.int64, (VarDim(comment="batch"))), "items": (torch.int64, (VarDim(comment="batch")))},
-        }
-
-    def output_describe(self):
-        return {
-            "train_step": {"loss": (float, [])},   # always 0.0: a memory-based model has no loss
-            "forward": {"unnormalized_scores": (torch.float32, [VarDim(comment="batch")])},
-        }
+    def _score_rows(self, csr, user_ids, out, stream):
+        P = _lib.ptr
+        _lib.check(_lib.lib().rk_itemknn_scores(self.num_items, int(self.k), P(self.nbr_id), P(self.nbr_w.data), *map(P, csr),
+                                                user_ids.numel(), P(user_ids), int(self.user_block or 0), P(out), stream), "rk_itemknn_scores")

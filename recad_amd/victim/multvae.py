@@ -133,7 +133,7 @@ class MultVAE(BaseVictim):
         return dev
 
     def _ratings(self, dev):
-        from ..defense.pca_select_users import rating_csr
+        from .._ratings import rating_csr
 
         if self._csr is None or self._csr[0] != dev:
             U, I, rowptr, col, _ = rating_csr(self.dataset, dev)

@@ -78,6 +78,35 @@ def test_gram_equals_the_integer_product(gpu_device, block, n):
         assert st.host().tolist() == [0, -1]
 
 
+def test_gram_over_two_bands(gpu_device):
+    """8192 + 65 items: the accumulators hold 8192 columns, so every row of A takes the band loop twice.  User 0 has some 300
+    entries over both bands (more than 128: its band segment is binary-searched), the other 39 have 6 to 102, fewer than 128
+    (strided whole and filtered); items 8191 and 8192, either side of the band edge, are rated by users 0 to 3.  The expected
+    matrix is built from the integer products of each user's entries; every bit of A is compared."""
+    n, U, lam = 8192 + 65, 40, 2.5
+    rng = np.random.default_rng(8257)
+    X = np.zeros((U, n), dtype=np.int64)
+    for u in range(U):
+        cnt = 300 if u == 0 else 6 + (u * 37) % 95
+        X[u, rng.choice(n, size=cnt, replace=False)] = rng.integers(1, 6, size=cnt)
+    X[:4, 8191:8193] = [[5, 1], [2, 3], [1, 1], [4, 2]]
+    lens = (X != 0).sum(axis=1)
+    assert lens[0] > 128 and lens[1:].max() < 128 and (X[0, :8192] != 0).sum() > 0 < (X[0, 8192:] != 0).sum()
+    D = np.zeros(n * n, dtype=np.int32)
+    for u in range(U):
+        c = np.nonzero(X[u])[0]
+        np.add.at(D, (c[:, None] * n + c[None, :]).reshape(-1), np.outer(X[u, c], X[u, c]).reshape(-1))
+    assert D.max() < 2 ** 24 and D[8191 * n + 8192] == 5 + 6 + 1 + 8
+    want = D.astype(np.float32)
+    del D
+    want[:: n + 1] = (want[:: n + 1] + np.float32(lam)).astype(np.float32)
+    rc, A, st = _gram(gpu_device, X, lam)
+    assert rc == 0, _lib.lib().rk_last_error()
+    got = A.host()
+    assert np.array_equal(_bits(got), _bits(want)), np.argwhere(_bits(got) != _bits(want))[:5]
+    assert st.host().tolist() == [0, -1]
+
+
 def _heavy_column(extra):
     """1044 (+ extra) users x 3 items: item 1 is rated 127 by 1040 users, then 55, 5, 2, 1: d_11 = 2^24 - 1; each extra user adds 1."""
     col = np.r_[np.full(1040, 127), [55, 5, 2, 1], np.ones(extra, dtype=np.int64)].astype(np.int64)
