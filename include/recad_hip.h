@@ -763,7 +763,9 @@ int rk_cs_scores(int32_t n_users, const int32_t *rowptr, const int64_t *pair_num
  * band: 0 = automatic (the items in equal bands of at most 8192), else a multiple of 64 in 64..RK_ITEMKNN_MAX_BAND.
  * 1 <= k <= RK_KNN_MAX_K.  order ([I] or NULL): a permutation of the items, workgroup b takes item order[b]; results do not
  * depend on it; an entry outside [0, I) is skipped.  Every slot of both tables is written.  Asynchronous.
- * RK_EINVAL with nothing launched and nothing written: k or band out of range, a missing pointer. */
+ * RK_EINVAL with nothing launched and nothing written: k or band out of range, a missing pointer.
+ * The entry does not care which side of the matrix it is pointed at: called on the transposed roles (the transpose as the CSR,
+ * the CSR as the transpose, the users' rnorm) it writes the user-user tables of the UserKNN victim, see below. */
 int rk_itemknn_neighbors(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val,
                          const int32_t *colptr, const int32_t *crow, const float *cval, const float *rnorm_item, int32_t k,
                          int32_t band, const int32_t *order /*[I] or NULL*/, int32_t *nbr_id /*[k*I]*/, float *nbr_w /*[k*I]*/,
@@ -858,6 +860,65 @@ int rk_rp3_scores(int32_t n_users, int32_t n_items, int32_t k, const int32_t *nb
 int rk_rp3_pair_scores(int32_t n_items, int32_t n_users, int32_t k, const int32_t *nbr_id, const float *nbr_w, const int32_t *rowptr,
                        const int32_t *col, const float *val, const int64_t *users /*[n]*/, const int64_t *items /*[n]*/, int64_t n,
                        float *out /*[n]*/, void *stream);
+
+/* UserKNN victim: user-neighbourhood collaborative filtering (Resnick et al. 1994; Breese, Heckerman and Kadie 1998; Herlocker
+ * et al. 1999), the recommender the average, segment and bandwagon profiles were designed against (Lam and Riedl 2004): the fake
+ * users are built to become neighbours of real ones.  Exact and repeatable.  It has no counterpart in the reference; the
+ * definition is this:
+ *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending) and its
+ *   transpose colptr / crow / cval (rk_pca_transpose);
+ *   q = (int) val; d_uv = sum_i q_ui q_vi in integers; n_u = d_uu < 2^31; r_u = (float)(1.0 / sqrt((double) n_u)), 0 for a user
+ *   with no ratings (rk_knn_norms of the matrix itself);
+ *   w_uv = ((float) d_uv * r_u) * r_v: one conversion, two fp32 multiplies in that order, no contraction: the operations and
+ *   order of the KnnSelectUsers definition, so the kept weights of user u are the topw of rk_knn_degsim, bit for bit;
+ *   neighbours of user u: every v != u with d_uv > 0 is a candidate, ordered by (w_uv descending, v ascending);
+ *   k_eff = min(k, U - 1); the first k_eff candidates fill slots t = 0, 1, ... of user u; unused slots hold id -1 and w = +0.0f;
+ *   layout, slot-major: nbr_id[t * n_users + u] (int32), nbr_w[t * n_users + u] (float32), t in [0, k);
+ *   the fit: NO neighbour kernel of its own.  The tables are written by rk_itemknn_neighbors on the transposed roles, called as
+ *     rk_itemknn_neighbors(n_users := I, n_items := U, rowptr := colptr, col := crow, val := cval, colptr := rowptr,
+ *                          crow := col, cval := val, rnorm_item := rnorm_user, k, band, order, nbr_id, nbr_w, stream):
+ *   that entry keeps the k largest (w descending, id ascending) per row of whichever side it is pointed at;
+ *   score(u, j), un-normalised: s_0 = +0.0f; for t = 0 .. k - 1 in ascending slot order, with v = id_t(u): if v has rated j,
+ *   s <- s + fl(w_t * (float) q_vj): fp32, two roundings per step, never a fused multiply-add.  Skipped: a slot with id -1, an
+ *   id outside [0, U) (a caller's own table), a neighbour who has not rated j.  Items u has rated are scored like any other;
+ *   excluding them is rk_topk_rows' job.  A user with no neighbours scores +0.0f everywhere;
+ *   score(u, j), normalize = 1: the weighted average of Breese et al. (1998) and Herlocker et al. (1999) without mean-centring:
+ *   den = the fp32 sum of w_t over the SAME slots (the kept neighbours who rated j) in the same order, plain adds from +0.0f;
+ *   the score is s / den by one IEEE fp32 division when den > 0, else +0.0f.  On implicit data (every q = 1) fl(w * 1) = w, so
+ *   numerator and denominator are the same bits and every item a kept neighbour has rated scores exactly 1.0f, every other one
+ *   +0.0f: the ranking is left to the tie rule of the selection.  That degeneracy belongs to the definition and is not worked
+ *   around; normalize is meant for ratings.
+ * w carries at most five roundings, each term one more and the sum k - 1 more: every un-normalised score lies within
+ * (k + 6) * 2^-24 * sum_t w_t q_t of the float64 evaluation of the same neighbour list (ItemKNN's count).  Normalised: the
+ * numerator as before (k + 6 units, relative, every term being >= 0), the denominator five roundings of w and k - 1 adds plus
+ * one unit for the second-order terms (k + 5), the quotient one more and one unit for the cross terms of the three: every
+ * score with den > 0 lies within (2 k + 13) * 2^-24 of the float64 quotient of the same list, relative.
+ * Not built: mean-centring (Resnick's deviation-from-mean prediction), significance weighting and shrinkage of the similarity,
+ * case amplification, inverse user frequency.
+ * recad_amd/victim/userknn.py drives these entries.  All pointers are device pointers. */
+/* The widest band of rk_userknn_scores: with normalize = 1 a column takes 8 bytes of LDS (numerator and denominator), which fit
+ * a CU's 160 KiB less the 64 bytes every kernel here leaves free.  The value is RK_RP3_MAX_BAND's, so that one band serves both. */
+#define RK_USERKNN_MAX_BAND 19904
+/* out[b * n_items + j] = score(user_ids[b], j) for b in [0, nb), every j: every element of out is written.  One wave per entry
+ * of user_ids, with an fp32 row of one band of columns in LDS (two rows when normalize = 1).  The wave reads the user's k ids
+ * and weights once, walks the slots in ascending order and spreads each neighbour's row over its lanes, 64 entries at a time:
+ * the columns of a row are distinct, so lanes never meet inside a slot, and LDS operations of a wave complete in program order,
+ * which gives every column its slot order (the same neighbour in two slots is added twice, in order).  A neighbour row longer
+ * than 128 entries is binary-searched for the band's segment, a shorter one is strided whole and filtered.  A catalogue wider
+ * than the band is so many passes; there is no catalogue cap.  band: 0 = automatic (equal bands of at most 8192), else a
+ * multiple of 64 in 64..RK_USERKNN_MAX_BAND.  user_ids ([nb], int32; repeats allowed): an id outside [0, U) scores +0.0f
+ * everywhere.  normalize: 0 or 1.  No float atomics.  Asynchronous; nb = 0 launches nothing.  RK_EINVAL with nothing launched
+ * and nothing written: k or band out of range, normalize outside {0, 1}, a missing pointer. */
+int rk_userknn_scores(int32_t n_users, int32_t n_items, int32_t k, const int32_t *nbr_id /*[k*U]*/, const float *nbr_w /*[k*U]*/,
+                      const int32_t *rowptr, const int32_t *col, const float *val, int32_t nb, const int32_t *user_ids,
+                      int32_t normalize, int32_t band, float *out /*[nb * n_items]*/, void *stream);
+/* out[p] = score(users[p], items[p]), p in [0, n): the same sum in the same order, so the same bits as the matrix entry.  A
+ * pair whose user or item id is out of range scores 0.0 and reads nothing.  One thread per pair: the item is looked up in each
+ * kept neighbour's ascending row.  Asynchronous; n = 0 launches nothing.  RK_EINVAL with nothing launched: k out of range,
+ * normalize outside {0, 1}, a missing pointer. */
+int rk_userknn_pair_scores(int32_t n_items, int32_t n_users, int32_t k, const int32_t *nbr_id, const float *nbr_w,
+                           const int32_t *rowptr, const int32_t *col, const float *val, const int64_t *users /*[n]*/,
+                           const int64_t *items /*[n]*/, int64_t n, int32_t normalize, float *out /*[n]*/, void *stream);
 
 /* EASE victim: the linear item-item autoencoder with a closed-form fit (Steck 2019, "Embarrassingly Shallow Autoencoders for
  * Sparse Data"), repeatable to the bit.  It has no counterpart in the reference; the definition is this:

@@ -28,6 +28,7 @@ RK_CS_FORM_AUTO, RK_CS_FORM_WAVE, RK_CS_FORM_WORKGROUP = 0, 1, 2
 RK_CS_SCORE_SYNC, RK_CS_SCORE_NORMALITY, RK_CS_SCORE_RESIDUAL = 0, 1, 2
 RK_ITEMKNN_MAX_BAND, RK_ITEMKNN_MAX_ITEMS, RK_ITEMKNN_MAX_USER_BLOCK = 39872, 163776, 16
 RK_RP3_MAX_BAND, RK_RP3_MAX_USERS = 19904, 1 << 23
+RK_USERKNN_MAX_BAND = 19904
 RK_EASE_MAX_ITEMS, RK_EASE_BLOCK_SMALL, RK_EASE_BLOCK_LARGE = 65536, 32, 64
 RK_EASE_BAD_GRAM, RK_EASE_NOT_SPD = 5, 6
 RK_IALS_MAX_DIM, RK_IALS_CHUNK, RK_IALS_GRAM_ROWS, RK_IALS_NOT_SPD = 128, 64, 256, 7
@@ -329,6 +330,8 @@ _SIGNATURES = {
     "rk_rp3_neighbors": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
     "rk_rp3_scores": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P],
     "rk_rp3_pair_scores": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P],
+    "rk_userknn_scores": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _I32, _P, _P],
+    "rk_userknn_pair_scores": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P, _P],
     "rk_ease_gram": [_I32, _I32, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P],
     "rk_ease_invert": [_I32, _P, _P, _I64, _I32, _P, _P],
     "rk_ease_weights": [_I32, _P, _P, _P],

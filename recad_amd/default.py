@@ -46,6 +46,9 @@ MODEL = {
         # build-specific (no reference counterpart): the random-walk item-item recommender (P3alpha, Cooper et al. 2014; RP3beta,
         # Christoffel et al. 2015), victim/rp3beta.py; beta = 0 is P3alpha; band None = automatic
         "rp3beta": {"alpha": 1.0, "beta": 0.6, "k": 100, "band": None},
+        # build-specific (no reference counterpart): user-neighbourhood CF (Resnick et al. 1994; Herlocker et al. 1999),
+        # victim/userknn.py; normalize True = the weighted average (for ratings), band None = automatic
+        "userknn": {"k": 50, "normalize": False, "band": None},
     },
     "attacker": {
         "random": {"attack_num": 50, "filler_num": 36},

@@ -4,7 +4,7 @@ from . import attack, defense, victim
 
 factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": victim.NCF,
                         "itemknn": victim.ItemKNN, "ease": victim.EASE, "ials": victim.IALS, "slim": victim.SLIM, "apr": victim.APR,
-                        "multvae": victim.MultVAE, "rp3beta": victim.RP3beta},
+                        "multvae": victim.MultVAE, "rp3beta": victim.RP3beta, "userknn": victim.UserKNN},
              "attacker": {"aia": attack.AIA, "aush": attack.Aush, "aushplus": attack.AushPlus, "random": attack.RandomAttacker,
                           "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack,
                           "uba": attack.UBA, "pga": attack.PGA},

@@ -9,5 +9,6 @@ from .multvae import MultVAE
 from .ncf import NCF
 from .rp3beta import RP3beta
 from .slim import SLIM
+from .userknn import UserKNN
 
-__all__ = ["APR", "BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "MultVAE", "NCF", "RP3beta", "SLIM"]
+__all__ = ["APR", "BaseVictim", "EASE", "IALS", "ItemKNN", "LightGCN", "MF", "MultVAE", "NCF", "RP3beta", "SLIM", "UserKNN"]
