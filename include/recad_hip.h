@@ -730,6 +730,63 @@ int rk_cs_user_sums(int32_t n_users, const int32_t *rowptr, const int32_t *col, 
 int rk_cs_scores(int32_t n_users, const int32_t *rowptr, const int64_t *pair_num, const int64_t *back_num, const int64_t *info,
                  int32_t mode, int32_t min_items, float *score /*[U]*/, void *stream);
 
+/* FraudarSelectUsers: greedy peeling towards the densest block of the bipartite rating graph (Hooi, Song, Beutel, Shah, Shin,
+ * Faloutsos, "FRAUDAR: Bounding Graph Fraud in the Face of Camouflage", KDD 2016), in integers end to end and repeatable.  It
+ * has no counterpart in the reference; the definition is this:
+ *   graph: users 0..U-1 and items 0..I-1; every stored entry of the rating CSR is one edge, its value is ignored; the nodes are
+ *   v in [0, N), N = U + I: user u is node u, item i is node U + i;
+ *   weights: deg_i = the stored entries of column i; w_i = wtab[deg_i], wtab a caller's table uint32 [U + 1] with every entry
+ *   met in 1..2^24 = RK_FD_WEIGHT_ONE (the Python layer builds it on the host in float64: rint(2^24 / ln(d + log_offset)) for
+ *   FRAUDAR's column weight, 2^24 throughout for plain densest-subgraph peeling, Charikar 2000); the degree is the ORIGINAL one,
+ *   the weights do not move during the peel;
+ *   priority, uint64: pri[u] = the sum of w_i over the user's items that are still alive; pri[U + i] = w_i * (the alive users
+ *   who rated i); nnz < 2^29 = RK_FD_MAX_NNZ, so every sum stays below 2^53;
+ *   peel: S_0 = all nodes, f_0 = sum_u pri[u]; at step t = 0 .. N - 1 the alive node v of least (pri, node id) is removed -- a
+ *   tie goes to the lower id, so a user goes before an item -- order[t] = v, step_of[v] = t, f_{t+1} = f_t - pri[v], and every
+ *   alive neighbour of v loses the weight of the item on that edge (a user v: w_i from each of its items; an item v: its own w
+ *   from each of its users); a removed node holds pri = 2^64 - 1 and is not charged again; S_t = {v : step_of[v] >= t},
+ *   n_t = N - t; f_t is the sum of the alive users' priorities at every t;
+ *   best block: t* = the least t in [0, N) that maximises f_t / n_t, compared exactly and strictly (f_a n_b > f_b n_a as a
+ *   128-bit product, so the earliest maximum wins); the block is S_t*; f_t* = 0 means an empty matrix and no block.
+ *   The greedy guarantee g(S_t*) >= max_S g(S) / 2, g(S) = f(S) / |S|, holds for any positive column weights, so for these.
+ * RK_FD_MAX_NODES: the peel keeps one (pri, id) minimum per 64 nodes, per 64 of those and so on in one workgroup's LDS, 16 bytes
+ * and one bit per entry; 2^19 nodes are the largest power of two whose 8323 entries fit 160 KiB.  The yelp shape (N = 89 106)
+ * runs; a graph of more nodes (config 4) is refused.
+ * Not built: rating-weighted edges, flagging items as a workflow step, batch peeling (Bahmani et al. 2012: another result).
+ * recad_amd/defense/fraudar_select_users.py drives these entries.  All pointers are device pointers.  nnz = rowptr[U]: the
+ * caller passes it so that the entries can refuse and bound on the host; a row or column range is clipped to [0, nnz), an id
+ * outside its range is skipped. */
+#define RK_FD_MAX_NODES (1 << 19)
+#define RK_FD_MAX_NNZ (1LL << 29)
+#define RK_FD_WEIGHT_ONE (1u << 24)
+#define RK_FD_STEPS_PER_LAUNCH 4096
+/* status[0] of rk_fd_init (the numbering continues RK_CS_*) */
+#define RK_FD_BAD_WEIGHT 19      /* wtab[d] outside 1..2^24 at a degree d some item has (0 included): status[1] is the lowest such d */
+#define RK_FD_BAD_DEGREE 20      /* colptr[i + 1] - colptr[i] outside 0..U: status[1] is the lowest such item; it goes before rule 19 */
+/* w_item[i] = wtab[deg_i], the initial priorities and info[3] = f_0 (info[0..2] are left alone).  One pass over the CSR, integer
+ * sums only.  Synchronous: reads status (device, int32[2]) back.  Without a violation status = {0, -1}.  With one: RK_EINVAL,
+ * status = {rule, index} and nothing else is written.  RK_EINVAL with nothing launched: a missing pointer, U or I negative,
+ * U + I outside 1..RK_FD_MAX_NODES, nnz outside 0..2^29 - 1. */
+int rk_fd_init(int32_t n_users, int32_t n_items, int64_t nnz, const int32_t *rowptr, const int32_t *col, const int32_t *colptr,
+               const uint32_t *wtab /*[U+1]*/, uint32_t *w_item /*[I]*/, uint64_t *pri /*[N]*/, int64_t *info /*[4]*/,
+               int32_t *status /*int32[2]*/, void *stream);
+/* The peel.  pri (in, destroyed: 2^64 - 1 everywhere afterwards) and w_item need not come from rk_fd_init: any uint32 weights
+ * and any priorities that are the sums defined above and stay below 2^63 peel exactly; f_0 is summed from pri.  order and
+ * step_of ([N]) are the permutation and its inverse; f_trace ([N] or NULL): f_trace[t] = f_t; info = {t*, f_t*, n_t*, f_0}.
+ * One 1024-thread workgroup; the chain is issued as ceil(N / steps_per_launch) launches on the stream, every launch rebuilds
+ * its LDS hierarchy and f from pri and takes the best block so far from info, so the words do not depend on
+ * steps_per_launch.  The column ids of a row (and the rows of a column) must be distinct: the neighbours of one node are
+ * updated by plain read-modify-writes.  Asynchronous.  RK_EINVAL with nothing launched: a missing pointer (f_trace may be
+ * NULL), U or I negative, U + I outside 1..RK_FD_MAX_NODES, nnz outside 0..2^29 - 1, steps_per_launch < 1. */
+int rk_fd_peel_ex(int32_t n_users, int32_t n_items, int64_t nnz, const int32_t *rowptr, const int32_t *col, const int32_t *colptr,
+                  const int32_t *crow, const uint32_t *w_item /*[I]*/, uint64_t *pri /*[N]*/, int32_t *order /*[N]*/,
+                  int32_t *step_of /*[N]*/, uint64_t *f_trace /*[N] or NULL*/, int64_t *info /*[4]*/, int32_t steps_per_launch,
+                  void *stream);
+/* the same with steps_per_launch = RK_FD_STEPS_PER_LAUNCH */
+int rk_fd_peel(int32_t n_users, int32_t n_items, int64_t nnz, const int32_t *rowptr, const int32_t *col, const int32_t *colptr,
+               const int32_t *crow, const uint32_t *w_item, uint64_t *pri, int32_t *order, int32_t *step_of, uint64_t *f_trace,
+               int64_t *info, void *stream);
+
 /* ItemKNN victim: item-neighbourhood collaborative filtering (Sarwar et al. 2001; Deshpande and Karypis 2004), exact and
  * repeatable.  It has no counterpart in the reference; the definition is this:
  *   input: the U x I rating CSR under the rules of rk_knn_norms (values integers in 1..127, columns strictly ascending);

@@ -26,6 +26,8 @@ RK_CS_MAX_CELLS, RK_CS_MAX_ITEMS = 8192, 1 << 26
 RK_CS_RULES = {17: "a negative deg_item or reach, or reach 0 at a rated item", 18: "more than RK_CS_MAX_CELLS cells"}
 RK_CS_FORM_AUTO, RK_CS_FORM_WAVE, RK_CS_FORM_WORKGROUP = 0, 1, 2
 RK_CS_SCORE_SYNC, RK_CS_SCORE_NORMALITY, RK_CS_SCORE_RESIDUAL = 0, 1, 2
+RK_FD_MAX_NODES, RK_FD_MAX_NNZ, RK_FD_WEIGHT_ONE, RK_FD_STEPS_PER_LAUNCH = 1 << 19, 1 << 29, 1 << 24, 4096
+RK_FD_RULES = {19: "a weight-table entry outside 1..2^24", 20: "a column length outside 0..n_users"}
 RK_ITEMKNN_MAX_BAND, RK_ITEMKNN_MAX_ITEMS, RK_ITEMKNN_MAX_USER_BLOCK = 39872, 163776, 16
 RK_RP3_MAX_BAND, RK_RP3_MAX_USERS = 19904, 1 << 23
 RK_USERKNN_MAX_BAND = 19904
@@ -322,6 +324,9 @@ _SIGNATURES = {
     "rk_cs_cells": [_I32, _P, _P, _I32, _P, _P, _P, _P, _P],
     "rk_cs_user_sums": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
     "rk_cs_scores": [_I32, _P, _P, _P, _P, _I32, _I32, _P, _P],
+    "rk_fd_init": [_I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "rk_fd_peel_ex": [_I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I32, _P],
+    "rk_fd_peel": [_I32, _I32, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "rk_itemknn_neighbors": [_I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I32, _I32, _P, _P, _P, _P],
     "rk_itemknn_scores": [_I32, _I32, _P, _P, _P, _P, _P, _I32, _P, _I32, _P, _P],
     "rk_itemknn_pair_scores": [_I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _I64, _P, _P],

@@ -94,7 +94,9 @@ MODEL = {
                  # build-specific (no reference counterpart): CatchSync synchronicity detection, defense/catchsync_select_users.py;
                  # form None = automatic by row length
                  "CatchSyncSelectUsers": {"score": "sync", "grid_bits": 1, "min_items": 20, "attack_num": 50, "schedule": "work",
-                                          "form": None}},
+                                          "form": None},
+                 # build-specific (no reference counterpart): FRAUDAR dense-block peeling, defense/fraudar_select_users.py
+                 "FraudarSelectUsers": {"weight": "log", "log_offset": 5.0, "select": "block", "n_blocks": 1, "attack_num": 50}},
 }
 for _scope in MODEL.values():
     for _cfg in _scope.values():

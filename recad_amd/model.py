@@ -9,7 +9,7 @@ factories = {"victim": {"lightgcn": victim.LightGCN, "mf": victim.MF, "ncf": vic
                           "average": attack.AverageAttack, "segment": attack.SegmentAttack, "bandwagon": attack.BandwagonAttack,
                           "uba": attack.UBA, "pga": attack.PGA},
              "defender": {"PCASelectUsers": defense.PCASelectUsers, "KnnSelectUsers": defense.KnnSelectUsers,
-                          "CatchSyncSelectUsers": defense.CatchSyncSelectUsers}}
+                          "CatchSyncSelectUsers": defense.CatchSyncSelectUsers, "FraudarSelectUsers": defense.FraudarSelectUsers}}
 
 
 def from_config(scope, name, **kwargs):
