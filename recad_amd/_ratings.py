@@ -81,12 +81,10 @@ def checked_norms(who, what, n_rows, n_cols, rowptr, col, val):
     L, P = _lib.lib(), _lib.ptr
     rnorm = torch.empty(n_rows, dtype=torch.float32, device=dev)
     status = torch.zeros(2, dtype=torch.int32, device=dev)
-    rc = L.rk_knn_norms(n_rows, n_cols, P(rowptr), P(col), P(val), P(rnorm), P(status), _lib.stream_ptr(dev))
-    if rc != 0:
-        rule, row = status.cpu().tolist()
-        if rule:
-            raise ValueError(f"{who}: the {what} breaks rule {rule} ({_lib.RK_KNN_RULES.get(rule, '?')}), first in row {row}")
-        _lib.check(rc, "rk_knn_norms")
+    bad = device_refusal(L.rk_knn_norms(n_rows, n_cols, P(rowptr), P(col), P(val), P(rnorm), P(status), _lib.stream_ptr(dev)),
+                         "rk_knn_norms", status)
+    if bad:
+        raise ValueError(f"{who}: the {what} breaks rule {bad[0]} ({_lib.RK_KNN_RULES.get(bad[0], '?')}), first in row {bad[1]}")
     return rnorm
 
 

@@ -26,7 +26,7 @@ static_assert(3LL * RK_APR_MAX_BATCH < (1LL << kAprIncBits), "3 b + role must fi
 __device__ __forceinline__ int apr_key_row(unsigned long long k) { return (int)((k >> kAprIncBits) & ((1ULL << kAprRowBits) - 1)); }
 __device__ __forceinline__ int apr_key_inc(unsigned long long k) { return (int)(k & ((1ULL << kAprIncBits) - 1)); }
 
-// ---- validation: reads the id arrays only.  First offending (triplet, rule) by a 64-bit atomicMin of t * 16 + rule.
+// ---- validation: reads the id arrays only.  First offending (triplet, rule) by rk_record_bad.
 __global__ void apr_check_kernel(const int64_t *__restrict__ users, const int64_t *__restrict__ pos, const int64_t *__restrict__ neg,
                                  long long n, int U, int I, unsigned long long *__restrict__ first_bad)
 {
@@ -36,16 +36,8 @@ __global__ void apr_check_kernel(const int64_t *__restrict__ users, const int64_
         if (u < 0 || u >= U) rule = RK_APR_BAD_USER;
         else if (i < 0 || i >= I) rule = RK_APR_BAD_POS;
         else if (j < 0 || j >= I) rule = RK_APR_BAD_NEG;
-        if (rule) atomicMin(first_bad, (unsigned long long)t * 16ULL + (unsigned long long)rule);
+        if (rule) rk_record_bad(first_bad, t, rule);
     }
-}
-
-__global__ void apr_status_kernel(const unsigned long long *__restrict__ first_bad, int *__restrict__ status)
-{
-    const unsigned long long k = *first_bad;
-    const bool ok = k == ~0ULL;
-    status[0] = ok ? 0 : (int)(k & 15ULL);
-    status[1] = ok ? -1 : (int)(k >> 4);
 }
 
 // ---- the plan
@@ -438,12 +430,11 @@ RK_EXPORT int rk_apr_train_epoch(const rk_apr_desc *desc, const int64_t *users, 
         RkScratch scratch(s);
         unsigned long long *first_bad = nullptr;
         RK_HIP(scratch.get(&first_bad, 1));
-        RK_HIP(hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long), s));
+        RK_HIP(rk_first_bad_arm(first_bad, 1, s));
         hipLaunchKernelGGL(apr_check_kernel, dim3((int)std::min<long long>((n + 255) / 256, 4096)), dim3(256), 0, s, users, pos, neg, (long long)n, U,
                            D.n_items, first_bad);
         RK_CHECK_LAUNCH();
-        hipLaunchKernelGGL(apr_status_kernel, dim3(1), dim3(1), 0, s, first_bad, status);
-        RK_CHECK_LAUNCH();
+        RK_HIP(rk_first_bad_status(first_bad, 1, status, s));
         int32_t h[2] = {0, 0};
         RK_HIP(hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, s));
         RK_HIP(hipStreamSynchronize(s));
@@ -548,18 +539,8 @@ __global__ void apr_group_check_kernel(const AprMember *__restrict__ members, un
         if (u < 0 || u >= U) rule = RK_APR_BAD_USER;
         else if (i < 0 || i >= I) rule = RK_APR_BAD_POS;
         else if (j < 0 || j >= I) rule = RK_APR_BAD_NEG;
-        if (rule) atomicMin(first_bad + blockIdx.y, (unsigned long long)t * 16ULL + (unsigned long long)rule);
+        if (rule) rk_record_bad(first_bad + blockIdx.y, t, rule);
     }
-}
-
-__global__ void apr_group_status_kernel(const unsigned long long *__restrict__ first_bad, int n_rep, int *__restrict__ status)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rep) return;
-    const unsigned long long k = first_bad[r];
-    const bool ok = k == ~0ULL;
-    status[2 * r] = ok ? 0 : (int)(k & 15ULL);
-    status[2 * r + 1] = ok ? -1 : (int)(k >> 4);
 }
 
 template <bool ADV>
@@ -707,11 +688,10 @@ RK_EXPORT int rk_apr_train_epoch_group(int32_t n_rep, const rk_apr_desc *descs, 
     RK_HIP(hipMemcpyAsync(d_coef, coef.data(), sizeof(AdamCoef) * coef.size(), hipMemcpyHostToDevice, s));
 
     {   // the ids of all members first: nothing else is launched on a bad one
-        RK_HIP(hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long) * (size_t)n_rep, s));
+        RK_HIP(rk_first_bad_arm(first_bad, (int)n_rep, s));
         hipLaunchKernelGGL(apr_group_check_kernel, dim3((int)std::min<long long>((max_n + 255) / 256, 4096), n_rep), dim3(256), 0, s, d_mem, first_bad);
         RK_CHECK_LAUNCH();
-        hipLaunchKernelGGL(apr_group_status_kernel, dim3(1), dim3(RK_APR_MAX_GROUP), 0, s, first_bad, (int)n_rep, status);
-        RK_CHECK_LAUNCH();
+        RK_HIP(rk_first_bad_status(first_bad, (int)n_rep, status, s));
         int32_t h[2 * RK_APR_MAX_GROUP];
         RK_HIP(hipMemcpyAsync(h, status, sizeof(int32_t) * 2 * (size_t)n_rep, hipMemcpyDeviceToHost, s));
         RK_HIP(hipStreamSynchronize(s));

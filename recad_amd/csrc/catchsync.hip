@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void cs_keys_kernel(int n_items, const int *__
     const int d = deg_item[i], r = reach[i];
     int k = -1;
     if (d < 0 || r < 0 || (d > 0 && r == 0)) {
-        atomicMin(first_bad, (unsigned long long)i * 32ULL + (unsigned long long)RK_CS_BAD_FEATURE);
+        rk_record_bad(first_bad, i, RK_CS_BAD_FEATURE);
     } else if (d > 0) {
         k = cs_bucket(d, s) * 256 + cs_bucket(r, s);
         atomicAdd(&cnt[k], 1);
@@ -122,16 +122,8 @@ __global__ __launch_bounds__(256) void cs_assign_kernel(int n_items, const int *
     if (i >= n_items) return;
     const int k = key[i];
     const int c = k < 0 ? -1 : rank[k];
-    if (c >= RK_CS_MAX_CELLS) atomicMin(first_bad, (unsigned long long)i * 32ULL + (unsigned long long)RK_CS_TOO_MANY_CELLS);
+    if (c >= RK_CS_MAX_CELLS) rk_record_bad(first_bad, i, RK_CS_TOO_MANY_CELLS);
     cell_of[i] = c;
-}
-
-__global__ void cs_status_kernel(const unsigned long long *__restrict__ first_bad, int *__restrict__ status)
-{
-    const unsigned long long k = *first_bad;
-    const bool ok = k == ~0ULL;
-    status[0] = ok ? 0 : (int)(k & 31ULL);
-    status[1] = ok ? -1 : (int)(k >> 5);
 }
 
 RK_EXPORT int rk_cs_cells(int32_t n_items, const int32_t *deg_item, const int32_t *reach, int32_t grid_bits, int32_t *cell_of,
@@ -151,7 +143,7 @@ RK_EXPORT int rk_cs_cells(int32_t n_items, const int32_t *deg_item, const int32_
     RK_HIP(scratch.get(&cell_tmp, (size_t)n_items));
     RK_HIP(scratch.get(&count_tmp, (size_t)RK_CS_MAX_CELLS));
     RK_HIP(scratch.get(&info_tmp, 4));
-    RK_HIP(hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long), s));
+    RK_HIP(rk_first_bad_arm(first_bad, 1, s));
     RK_HIP(rk_zero_async(tab, sizeof(int) * (size_t)kCsKeys, s));
     const int grid = (n_items + 255) / 256;
     hipLaunchKernelGGL(cs_keys_kernel, dim3(grid), dim3(256), 0, s, n_items, deg_item, reach, grid_bits, key, tab, first_bad);
@@ -160,8 +152,7 @@ RK_EXPORT int rk_cs_cells(int32_t n_items, const int32_t *deg_item, const int32_
     RK_CHECK_LAUNCH();
     hipLaunchKernelGGL(cs_assign_kernel, dim3(grid), dim3(256), 0, s, n_items, key, tab + kCsKeys, cell_tmp, first_bad);
     RK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(cs_status_kernel, dim3(1), dim3(1), 0, s, first_bad, status);
-    RK_CHECK_LAUNCH();
+    RK_HIP(rk_first_bad_status(first_bad, 1, status, s));
     int32_t h[2] = {0, 0};
     RK_HIP(hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, s));
     RK_HIP(hipStreamSynchronize(s));

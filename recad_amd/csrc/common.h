@@ -154,6 +154,46 @@ static inline hipError_t rk_zero_async(void *p, size_t bytes, hipStream_t s)
     return hipGetLastError();
 }
 
+// How an entry point refuses its input on the device.  A check kernel records each break in a 64-bit word armed to all ones:
+// atomicMin of index * 32 + rule leaves the lowest index and, at that index, the lowest rule.  Five rule bits hold every rule
+// number of include/recad_hip.h (the largest is RK_FD_BAD_DEGREE).  rk_first_bad_status then decodes n such words into
+// status[2 r] = rule, status[2 r + 1] = index, (0, -1) for a word nothing was recorded in.
+static constexpr int kRkRuleBits = 5;
+static_assert(RK_FD_BAD_DEGREE < (1 << kRkRuleBits), "a rule number must fit the low bits of a first_bad word");
+__device__ __forceinline__ void rk_record_bad(unsigned long long *first_bad, long long index, int rule)
+{
+    atomicMin(first_bad, ((unsigned long long)index << kRkRuleBits) + (unsigned long long)rule);
+}
+static __global__ void rk_first_bad_status_kernel(const unsigned long long *__restrict__ first_bad, int n, int *__restrict__ status)
+{
+    for (int r = threadIdx.x; r < n; r += blockDim.x) {
+        const unsigned long long k = first_bad[r];
+        const bool ok = k == ~0ULL;
+        status[2 * r] = ok ? 0 : (int)(k & ((1ULL << kRkRuleBits) - 1));
+        status[2 * r + 1] = ok ? -1 : (int)(k >> kRkRuleBits);
+    }
+}
+static inline hipError_t rk_first_bad_arm(unsigned long long *first_bad, int n, hipStream_t s)
+{
+    return hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long) * (size_t)n, s);
+}
+static inline hipError_t rk_first_bad_status(const unsigned long long *first_bad, int n, int *status, hipStream_t s)
+{
+    hipLaunchKernelGGL(rk_first_bad_status_kernel, dim3(1), dim3(64), 0, s, first_bad, n, status);
+    return hipGetLastError();
+}
+// status <- (rule, index) by one thread: an entry point's opening (0, -1) or what its host side has decided
+static __global__ void rk_set_status_kernel(int *status, int rule, int index)
+{
+    status[0] = rule;
+    status[1] = index;
+}
+static inline hipError_t rk_set_status(int *status, int rule, int index, hipStream_t s)
+{
+    hipLaunchKernelGGL(rk_set_status_kernel, dim3(1), dim3(1), 0, s, status, rule, index);
+    return hipGetLastError();
+}
+
 // Adam coefficients for 1-based step t, torch.optim.Adam single-tensor math:
 // step_size = lr / (1 - b1^t); bc2s = sqrt(1 - b2^t).  Computed in double like Python does.
 struct AdamCoef {

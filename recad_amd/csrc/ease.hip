@@ -23,17 +23,6 @@ static_assert(RK_EASE_BLOCK_LARGE == kEaTile && RK_EASE_BLOCK_SMALL == 32, "a pi
 static_assert((long long)RK_EASE_MAX_ITEMS / kEaTile <= 65535, "the trailing grid's y dimension");
 
 // ---- gram
-__global__ void ease_status_kernel(int *status, int rule, int index)
-{
-    status[0] = rule;
-    status[1] = index;
-}
-static inline hipError_t ea_set_status(int *status, int rule, int index, hipStream_t s)
-{
-    hipLaunchKernelGGL(ease_status_kernel, dim3(1), dim3(1), 0, s, status, rule, index);
-    return hipGetLastError();
-}
-
 // status[1] <- the lowest item whose d_ii reaches 2^24; one wave per item
 __global__ __launch_bounds__(256) void ease_diag_check_kernel(int n_items, const int *__restrict__ colptr, const float *__restrict__ cval,
                                                               int *__restrict__ status)
@@ -99,13 +88,13 @@ RK_EXPORT int rk_ease_gram(int32_t n_users, int32_t n_items, const int32_t *rowp
     if (!isfinite(lambda) || !(lambda > 0.0f)) RK_FAIL(RK_EINVAL, "rk_ease_gram: lambda = %g is not a finite positive number", (double)lambda);
     hipStream_t s = (hipStream_t)stream;
     int st[2] = {0, INT_MAX};
-    RK_HIP(ea_set_status(status, 0, INT_MAX, s));
+    RK_HIP(rk_set_status(status, 0, INT_MAX, s));
     hipLaunchKernelGGL(ease_diag_check_kernel, dim3((n_items + 3) / 4), dim3(256), 0, s, n_items, colptr, cval, status);
     RK_CHECK_LAUNCH();
     RK_HIP(hipMemcpyAsync(st, status, sizeof(st), hipMemcpyDeviceToHost, s));
     RK_HIP(hipStreamSynchronize(s));
     const bool bad = st[1] != INT_MAX;
-    RK_HIP(ea_set_status(status, bad ? RK_EASE_BAD_GRAM : 0, bad ? st[1] : -1, s));
+    RK_HIP(rk_set_status(status, bad ? RK_EASE_BAD_GRAM : 0, bad ? st[1] : -1, s));
     if (bad) RK_FAIL(RK_EINVAL, "rk_ease_gram: item %d has a squared norm of 2^24 or more", st[1]);
     hipLaunchKernelGGL(ease_gram_kernel, dim3(n_items), dim3(kEaThreads), 0, s, n_users, n_items, rowptr, col, val, colptr, crow, cval,
                        lambda, A);
@@ -255,7 +244,7 @@ RK_EXPORT int rk_ease_invert(int32_t n_items, float *A, float *work, int64_t wor
                 (long long)n_items * b, n_items, b);
     hipStream_t s = (hipStream_t)stream;
     int st[2] = {0, -1};
-    RK_HIP(ea_set_status(status, 0, -1, s));
+    RK_HIP(rk_set_status(status, 0, -1, s));
     const int nT = (n_items + kEaTile - 1) / kEaTile;
     for (int k0 = 0; k0 < n_items; k0 += b) {
         const int bk = std::min(b, n_items - k0);

@@ -83,6 +83,7 @@ __global__ __launch_bounds__(256) void fd_check_kernel(int n_users, int n_items,
     if (w < 1u || w > RK_FD_WEIGHT_ONE) atomicMin(&bad[1], (unsigned long long)d);
 }
 
+// not rk_first_bad_status_kernel: two words, one per rule, and the degree rule goes first whatever the indices
 __global__ void fd_status_kernel(const unsigned long long *__restrict__ bad, int *__restrict__ status)
 {
     const bool deg = bad[0] != ~0ULL, wt = bad[1] != ~0ULL;

@@ -7,12 +7,6 @@
 // without the dense matrix.  Nothing here adds floats atomically: every sum has one owner and a fixed order.
 #include "ials_solve.h"
 
-__global__ void ials_status_kernel(int *status)
-{
-    status[0] = 0;
-    status[1] = -1;
-}
-
 template <int NT>
 __global__ __launch_bounds__(kIaThreads) void ials_half_sweep_kernel(int n_rows, int n_cols, int d, const float *__restrict__ G,
                                                                      const int *__restrict__ rowptr, const int *__restrict__ col,
@@ -276,8 +270,7 @@ RK_EXPORT int rk_ials_half_sweep(int32_t n_rows, int32_t n_cols, int32_t d, cons
     hipStream_t s = (hipStream_t)stream;
     const int dp = ia_dp(d);
     const size_t lds = sizeof(float) * ia_lds_floats(dp, true);
-    hipLaunchKernelGGL(ials_status_kernel, dim3(1), dim3(1), 0, s, status);
-    RK_CHECK_LAUNCH();
+    RK_HIP(rk_set_status(status, 0, -1, s));
 #define IA_CALL(NT)                                                                                                                   \
     hipLaunchKernelGGL(ials_half_sweep_kernel<NT>, dim3(n_rows), dim3(kIaThreads), lds, s, n_rows, n_cols, d, G, rowptr, col, val, alpha, Y, \
                        order, X_out, status)

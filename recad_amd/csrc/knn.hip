@@ -17,7 +17,7 @@ static_assert(4 * RK_KNN_MAX_BAND + kKnnScratchBytes <= kLdsMaxBytes - 64, "RK_K
 static_assert(RK_KNN_MAX_BAND % 64 == 0 && RK_KNN_MAX_K == 128, "the final sort is written for 128 slots");
 static constexpr int kKnnAutoBand = 8192;                       // automatic band: 41 KiB per workgroup, 3 workgroups per CU
 
-// ---- norms and validation: one wave per row.  First offending (row, rule) by a 64-bit atomicMin of row * 8 + rule.
+// ---- norms and validation: one wave per row.  First offending (row, rule) by rk_record_bad.
 __global__ __launch_bounds__(256) void knn_norms_kernel(int n_users, int n_items, const int *__restrict__ rowptr,
                                                         const int *__restrict__ col, const float *__restrict__ val,
                                                         float *__restrict__ rnorm, unsigned long long *__restrict__ first_bad)
@@ -47,18 +47,10 @@ __global__ __launch_bounds__(256) void knn_norms_kernel(int n_users, int n_items
     }
     if (lane != 0) return;
     if (rule) {
-        atomicMin(first_bad, (unsigned long long)r * 8ULL + (unsigned long long)rule);
+        rk_record_bad(first_bad, r, rule);
         return;
     }
     rnorm[r] = n > 0 ? (float)(1.0 / sqrt((double)n)) : 0.0f;      // fp64 sqrt and divide are correctly rounded (hipcc's default)
-}
-
-__global__ void knn_status_kernel(const unsigned long long *__restrict__ first_bad, int *__restrict__ status)
-{
-    const unsigned long long k = *first_bad;
-    const bool ok = k == ~0ULL;
-    status[0] = ok ? 0 : (int)(k & 7ULL);
-    status[1] = ok ? -1 : (int)(k >> 3);
 }
 
 RK_EXPORT int rk_knn_norms(int32_t n_users, int32_t n_items, const int32_t *rowptr, const int32_t *col, const float *val, float *rnorm,
@@ -71,11 +63,10 @@ RK_EXPORT int rk_knn_norms(int32_t n_users, int32_t n_items, const int32_t *rowp
     float *tmp = nullptr;
     RK_HIP(scratch.get(&first_bad, 1));
     RK_HIP(scratch.get(&tmp, (size_t)n_users));
-    RK_HIP(hipMemsetAsync(first_bad, 0xff, sizeof(unsigned long long), s));
+    RK_HIP(rk_first_bad_arm(first_bad, 1, s));
     hipLaunchKernelGGL(knn_norms_kernel, dim3((n_users + 3) / 4), dim3(256), 0, s, n_users, n_items, rowptr, col, val, tmp, first_bad);
     RK_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_status_kernel, dim3(1), dim3(1), 0, s, first_bad, status);
-    RK_CHECK_LAUNCH();
+    RK_HIP(rk_first_bad_status(first_bad, 1, status, s));
     int32_t h[2] = {0, 0};
     RK_HIP(hipMemcpyAsync(h, status, sizeof(h), hipMemcpyDeviceToHost, s));
     RK_HIP(hipStreamSynchronize(s));

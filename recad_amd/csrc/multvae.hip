@@ -20,7 +20,7 @@ static constexpr int kMvPosBits = 12;                         // a batch positio
 static constexpr unsigned long long kMvHashMul = 0xD1342543DE82EF95ULL, kMvEpsStream = 0xA5A5A5A5A5A5A5A5ULL;
 static_assert(RK_MVAE_MAX_BATCH == (1 << kMvPosBits), "a batch position must fit the key's low bits");
 
-// ---- validation: reads the ids and the rating rows only.  First offending (row, rule) by a 64-bit atomicMin of t * 32 + rule;
+// ---- validation: reads the ids and the rating rows only.  First offending (row, rule) by rk_record_bad;
 // rows_too (training) also walks each row and adds its length to its step's count (integer atomics).
 __global__ void mv_check_kernel(const int *__restrict__ ids, long long n, int U, int I, const int *__restrict__ rowptr,
                                 const int *__restrict__ col, int rows_too, int batch, unsigned long long *__restrict__ step_nnz,
@@ -43,10 +43,11 @@ __global__ void mv_check_kernel(const int *__restrict__ ids, long long n, int U,
                 if (!rule) atomicAdd(step_nnz + t / batch, (unsigned long long)(e - b));
             }
         }
-        if (rule) atomicMin(first_bad, (unsigned long long)t * 32ULL + (unsigned long long)rule);
+        if (rule) rk_record_bad(first_bad, t, rule);
     }
 }
 
+// not rk_first_bad_status_kernel: a clean first_bad word is followed by the steps' counts against nnz_cap
 __global__ void mv_status_kernel(const unsigned long long *__restrict__ first_bad, const unsigned long long *__restrict__ step_nnz,
                                  int n_steps, long long nnz_cap, int *__restrict__ status)
 {
@@ -346,7 +347,7 @@ __global__ void mv_pair_kernel(int n, int H, const float *__restrict__ h2, const
 __global__ void mv_items_check_kernel(const int *__restrict__ items, long long n, int I, unsigned long long *__restrict__ first_bad)
 {
     for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x)
-        if (items[t] < 0 || items[t] >= I) atomicMin(first_bad, (unsigned long long)t * 32ULL + (unsigned long long)RK_MVAE_BAD_ITEM);
+        if (items[t] < 0 || items[t] >= I) rk_record_bad(first_bad, t, RK_MVAE_BAD_ITEM);
 }
 
 // ---- host

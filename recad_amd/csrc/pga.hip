@@ -12,12 +12,6 @@ static constexpr int kPgEntryChunk = 256;                         // entries of 
 static_assert(RK_PGA_MAX_TARGETS <= kPgThreads, "one thread pins one target");
 
 // ---------------------------------------------------------------------------------------------------- rk_ials_solve_rhs
-__global__ void pga_status_kernel(int *status)
-{
-    status[0] = 0;
-    status[1] = -1;
-}
-
 template <int NT>
 __global__ __launch_bounds__(kIaThreads) void ials_solve_rhs_kernel(int n_rows, int n_cols, int d, const float *__restrict__ G,
                                                                     const int *__restrict__ rowptr, const int *__restrict__ col,
@@ -73,8 +67,7 @@ RK_EXPORT int rk_ials_solve_rhs(int32_t n_rows, int32_t n_cols, int32_t d, const
     hipStream_t s = (hipStream_t)stream;
     const int dp = ia_dp(d);
     const size_t lds = sizeof(float) * ia_lds_floats(dp, true);
-    hipLaunchKernelGGL(pga_status_kernel, dim3(1), dim3(1), 0, s, status);
-    RK_CHECK_LAUNCH();
+    RK_HIP(rk_set_status(status, 0, -1, s));
 #define IA_CALL(NT)                                                                                                                  \
     hipLaunchKernelGGL(ials_solve_rhs_kernel<NT>, dim3(n_rows), dim3(kIaThreads), lds, s, n_rows, n_cols, d, G, rowptr, col, val, alpha, Y, \
                        rhs, order, X_out, status)

@@ -20,17 +20,6 @@ static_assert(2 * kSlWaves * (sizeof(float) + sizeof(int)) == kSlScratchBytes, "
 static_assert(8LL * RK_SLIM_MAX_ITEMS + kSlScratchBytes <= kLdsMaxBytes - 64, "RK_SLIM_MAX_ITEMS does not fit a CU's LDS");
 static_assert(8LL * (RK_SLIM_MAX_ITEMS + 1) + kSlScratchBytes > kLdsMaxBytes - 64, "RK_SLIM_MAX_ITEMS is not the largest catalogue");
 
-__global__ void slim_status_kernel(int *status, int rule, int index)
-{
-    status[0] = rule;
-    status[1] = index;
-}
-static inline hipError_t sl_set_status(int *status, int rule, int index, hipStream_t s)
-{
-    hipLaunchKernelGGL(slim_status_kernel, dim3(1), dim3(1), 0, s, status, rule, index);
-    return hipGetLastError();
-}
-
 // status[1] <- the lowest k whose G_kk is not a finite number > 0
 __global__ __launch_bounds__(256) void slim_diag_check_kernel(int n, const float *__restrict__ G, int *__restrict__ status)
 {
@@ -174,13 +163,13 @@ RK_EXPORT int rk_slim_fit(int32_t n_items, const float *G, float l1, int32_t swe
     if (!isfinite(l1) || !(l1 >= 0.0f)) RK_FAIL(RK_EINVAL, "rk_slim_fit: l1 = %g is not a finite number >= 0", (double)l1);
     hipStream_t s = (hipStream_t)stream;
     int st[2] = {0, INT_MAX};
-    RK_HIP(sl_set_status(status, 0, INT_MAX, s));
+    RK_HIP(rk_set_status(status, 0, INT_MAX, s));
     hipLaunchKernelGGL(slim_diag_check_kernel, dim3((n_items + 255) / 256), dim3(256), 0, s, n_items, G, status);
     RK_CHECK_LAUNCH();
     RK_HIP(hipMemcpyAsync(st, status, sizeof(st), hipMemcpyDeviceToHost, s));
     RK_HIP(hipStreamSynchronize(s));
     const bool bad = st[1] != INT_MAX;
-    RK_HIP(sl_set_status(status, bad ? RK_SLIM_BAD_DIAG : 0, bad ? st[1] : -1, s));
+    RK_HIP(rk_set_status(status, bad ? RK_SLIM_BAD_DIAG : 0, bad ? st[1] : -1, s));
     if (bad) RK_FAIL(RK_EINVAL, "rk_slim_fit: diagonal entry %d is not a finite positive number", st[1]);
     static RkPerDeviceOnce attr_once;
     int attr_dev;

@@ -20,10 +20,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .._ratings import checked_norms, device_refusal, rating_csr, transposed
-from ..utils import get_logger
-from ..victim.base import BaseVictim
-from .pca_select_users import flag_count
+from .._ratings import checked_norms, device_refusal, transposed
+from ._select_users import SelectUsersDefender, flag_count
 
 WEIGHTS = ("log", "degree")
 SELECTS = ("block", "count")
@@ -63,52 +61,27 @@ def without_block(U, rowptr, col, val, in_block):
     return new_ptr, col[keep].contiguous(), val[keep].contiguous()
 
 
-class FraudarSelectUsers(BaseVictim):
-    """Lazy like CatchSyncSelectUsers: ``model.from_config("defender", "FraudarSelectUsers", select="count", attack_num=50)``
+class FraudarSelectUsers(SelectUsersDefender):
+    """Lazy through SelectUsersDefender: ``model.from_config("defender", "FraudarSelectUsers", select="count", attack_num=50)``
     keeps the configuration, ``.I(dataset=...)`` builds it, ``defense_step()`` returns the flagged user ids.  Afterwards
     ``step_of``, ``order`` (device int32 [U + I]), ``info`` (device int64 [4]: t*, f, n, f_0) and ``w_item`` (device uint32 words
     in an int32 tensor [I]) describe the first round's peel, ``blocks`` every round's block, ``predLabels`` and ``ranking`` the
     step."""
 
     victim_name = "FraudarSelectUsers"
-    scope = "defender"
 
     def _build(self, weight, log_offset, select, n_blocks, attack_num, **config):
-        self.dataset = config.get("dataset")
-        self.device = torch.device(config.get("device", "cuda"))
         self.weight, self.log_offset, self.select, self.n_blocks = weight, log_offset, select, n_blocks
         self.attack_num = int(attack_num)
-        self.logger = get_logger(__name__, level=config.get("logging_level", 20))
         self._clear()
-        self._shape()
+        self._open(config)
 
     def _clear(self):
         self.step_of = self.order = self.info = self.w_item = self.blocks = self.predLabels = None
         self._ranking = None
 
-    def _shape(self):
-        ds = self.dataset
-        if ds is None:        # the defence workflow may hand the dataset to defense_step() instead
-            self.user_num = self.item_num = None
-        elif hasattr(ds, "info_describe") and not isinstance(ds, (tuple, list)):
-            info = ds.info_describe()
-            self.user_num, self.item_num = int(info["n_users"]), int(info["n_items"])
-        elif isinstance(ds, (tuple, list)):
-            self.user_num, self.item_num = len(ds[0]) - 1, (int(ds[3]) if len(ds) == 4 else None)
-        else:
-            self.user_num, self.item_num = int(ds.shape[0]), int(ds.shape[1])
-
-    def forward(self):
-        pass
-
-    def train_step(self, **config):
-        pass
-
-    def input_describe(self):
-        return {"defense_step": {"dataset": (object, [])}}
-
-    def output_describe(self):
-        return {"defense_step": {"spam_list": (list, [])}}
+    def _check(self):
+        check_config(self.weight, self.log_offset, self.select, self.n_blocks)
 
     def _peel(self, U, I, rowptr, col, val):
         """One round on a non-empty CSR: transpose, weights, rk_fd_init, rk_fd_peel -> (step_of, order, info, w_item)."""
@@ -133,19 +106,8 @@ class FraudarSelectUsers(BaseVictim):
                    "rk_fd_peel")
         return step_of, order, info, w_item
 
-    def defense_step(self, **config):
-        """The peel on the device, then the users of the densest block(s) or the users removed last.  `dataset=` (optional)
-        replaces the dataset given at .I()."""
-        check_config(self.weight, self.log_offset, self.select, self.n_blocks)
-        if config.get("dataset") is not None:
-            self.dataset = config["dataset"]
-            self._shape()
-        if self.dataset is None:
-            raise ValueError("FraudarSelectUsers.defense_step: no dataset (give one to .I() or to defense_step)")
-        _lib.require_gpu()
-        dev = self.device
-        U, I, rowptr, col, val = rating_csr(self.dataset, dev)
-        self.user_num, self.item_num = U, I
+    def _detect(self, U, I, rowptr, col, val):
+        """The peel on the device, then the users of the densest block(s) or the users removed last."""
         if U + I > _lib.RK_FD_MAX_NODES:
             raise ValueError(f"FraudarSelectUsers: {U} users + {I} items, at most RK_FD_MAX_NODES = {_lib.RK_FD_MAX_NODES} nodes")
         self._clear()

@@ -9,14 +9,11 @@ U x U matrix, and tests/_knn_restate.py restates it in numpy, bit for bit.
 share few items with anybody, and on this project's implicit ml1m-shaped synthetic data 48 of 50 injected profiles are among
 the 50 lowest.  ``select="high"`` flags the largest, the side Chirita's explicit-rating / Pearson
 setting reports.  Nobody has measured either on real data."""
-import numpy as np
 import torch
 
 from .. import _lib
-from .._ratings import checked_norms, rating_csr, transposed
-from ..utils import get_logger
-from ..victim.base import BaseVictim
-from .pca_select_users import flag_count
+from .._ratings import checked_norms, transposed
+from ._select_users import SelectUsersDefender
 
 SELECTS = ("low", "high")
 SCHEDULES = ("work", "natural")
@@ -44,60 +41,25 @@ def work_order(rowptr, col, colptr):
     return torch.sort(work, descending=True, stable=True).indices.to(torch.int32).contiguous()
 
 
-class KnnSelectUsers(BaseVictim):
-    """Lazy like PCASelectUsers: ``model.from_config("defender", "KnnSelectUsers", k=25, attack_num=50)`` keeps the
+class KnnSelectUsers(SelectUsersDefender):
+    """Lazy through SelectUsersDefender: ``model.from_config("defender", "KnnSelectUsers", k=25, attack_num=50)`` keeps the
     configuration, ``.I(dataset=...)`` builds it, ``defense_step()`` returns the flagged user ids.  Afterwards ``scores``
     (device [U]), ``top_similarities`` (device [U, k]), ``predLabels`` and ``ranking`` describe the step."""
 
     victim_name = "KnnSelectUsers"
-    scope = "defender"
 
     def _build(self, k, attack_num, select, band, schedule, **config):
-        self.dataset = config.get("dataset")
-        self.device = torch.device(config.get("device", "cuda"))
         self.k, self.attack_num, self.select, self.band, self.schedule = k, int(attack_num), select, band, schedule
-        self.logger = get_logger(__name__, level=config.get("logging_level", 20))
         self.scores = self.top_similarities = self.predLabels = None
-        self._order = self._ranking = None
-        self._shape()
+        self._open(config)
 
-    def _shape(self):
-        ds = self.dataset
-        if ds is None:        # the defence workflow may hand the dataset to defense_step() instead
-            self.user_num = self.item_num = None
-        elif hasattr(ds, "info_describe") and not isinstance(ds, (tuple, list)):
-            info = ds.info_describe()
-            self.user_num, self.item_num = int(info["n_users"]), int(info["n_items"])
-        elif isinstance(ds, (tuple, list)):
-            self.user_num, self.item_num = len(ds[0]) - 1, (int(ds[3]) if len(ds) == 4 else None)
-        else:
-            self.user_num, self.item_num = int(ds.shape[0]), int(ds.shape[1])
-
-    def forward(self):
-        pass
-
-    def train_step(self, **config):
-        pass
-
-    def input_describe(self):
-        return {"defense_step": {"dataset": (object, [])}}
-
-    def output_describe(self):
-        return {"defense_step": {"spam_list": (list, [])}}
-
-    def defense_step(self, **config):
-        """DegSim of every user on the device, then the flag_count(attack_num, U) users of smallest (select="low") or largest
-        (select="high") DegSim, ties to the lower id.  `dataset=` (optional) replaces the dataset given at .I()."""
+    def _check(self):
         check_config(self.k, self.select, self.band, self.schedule)
-        if config.get("dataset") is not None:
-            self.dataset = config["dataset"]
-            self._shape()
-        if self.dataset is None:
-            raise ValueError("KnnSelectUsers.defense_step: no dataset (give one to .I() or to defense_step)")
-        _lib.require_gpu()
+
+    def _detect(self, U, I, rowptr, col, val):
+        """DegSim of every user on the device, then the flag_count(attack_num, U) users of smallest (select="low") or largest
+        (select="high") DegSim, ties to the lower id."""
         dev, k = self.device, int(self.k)
-        U, I, rowptr, col, val = rating_csr(self.dataset, dev)
-        self.user_num, self.item_num = U, I
         L, P, s = _lib.lib(), _lib.ptr, _lib.stream_ptr(dev)
         rnorm = checked_norms("KnnSelectUsers", "rating matrix", U, I, rowptr, col, val)    # nothing further is launched after a refusal
         colptr, crow, cval = transposed(U, I, rowptr, col, val)
@@ -108,22 +70,11 @@ class KnnSelectUsers(BaseVictim):
                                    P(order), P(topw), P(degsim), s), "rk_knn_degsim")
         ranked = torch.empty(U, dtype=torch.int32, device=dev)
         _lib.check(L.rk_knn_select(U, P(degsim), U, int(self.select == "high"), P(ranked), s), "rk_knn_select")
-        self.scores, self.top_similarities, self._order = degsim, topw, ranked
-        m = flag_count(self.attack_num, U)
-        spam = ranked[:m].cpu().numpy().astype(np.int64)
-        self.predLabels = np.zeros(U)
-        self.predLabels[spam] = 1
-        self._ranking = None
-        return spam.tolist()
+        self.scores, self.top_similarities = degsim, topw
+        return self._flag(ranked, U)
 
     @property
     def ranking(self):
         """[(user id, DegSim)] in flag order (ascending for select="low", descending for "high"; ties to the lower id),
         built on first use."""
-        if self._order is None:
-            return None
-        if self._ranking is None:
-            o = self._order.cpu().numpy()
-            d = self.scores.cpu().numpy()[o]
-            self._ranking = list(zip(o.tolist(), d.astype(np.float64).tolist()))
-        return self._ranking
+        return self._pairs(self.scores)

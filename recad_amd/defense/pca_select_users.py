@@ -12,24 +12,12 @@ and O(I*b) step runs in HIP (csrc/pca.hip); only b x b fp64 matrices travel to t
 Sign convention (the one deliberate departure from the reference, whose ARPACK signs are arbitrary): every
 eigenvector is flipped so that its entry of largest magnitude is positive, the lowest index winning a tie.
 """
-import math
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .._ratings import rating_csr  # noqa: F401  (callers import it from here as well)
-from ..utils import get_logger
-from ..victim.base import BaseVictim
-
-_logger = get_logger(__name__)
-
-
-def flag_count(attack_num, n_users):
-    """Number of users the reference flags: #{i >= 0 : i < (attack_num / U) * U} in float64 (PCASelectUsers.py:34,85),
-    which rounding can make attack_num + 1.  Capped at U."""
-    bound = (attack_num / n_users) * n_users
-    return min(int(n_users), max(0, math.ceil(bound)))
+from ._select_users import SelectUsersDefender, flag_count  # noqa: F401  (flag_count: callers import it from here as well)
 
 
 def effective_k(k, n_users, n_items):
@@ -178,61 +166,23 @@ def subspace_eigs(op, k, b, tol=1e-5, max_iter=300, seed=2023):
                        f"residuals / lambda_1 = {[float(r) for r in (res[:k] / lam[0])]} > tol {tol}")
 
 
-class PCASelectUsers(BaseVictim):
-    """Lazy like the reference: ``model.from_config("defender", "PCASelectUsers", kVals=3, attack_num=50)`` keeps the
-    configuration, ``.I(dataset=...)`` builds it, ``defense_step()`` returns the flagged user ids.  Afterwards
-    ``eigenvalues``, ``eigenvectors``, ``distances``, ``predLabels`` and ``disSort`` hold what the reference's
+class PCASelectUsers(SelectUsersDefender):
+    """Lazy like the reference, through SelectUsersDefender: ``model.from_config("defender", "PCASelectUsers", kVals=3,
+    attack_num=50)`` keeps the configuration, ``.I(dataset=...)`` builds it, ``defense_step()`` returns the flagged user ids.
+    Afterwards ``eigenvalues``, ``eigenvectors``, ``distances``, ``predLabels`` and ``disSort`` hold what the reference's
     attributes hold (eigenvectors / distances as device tensors)."""
 
     victim_name = "PCASelectUsers"
-    scope = "defender"
 
     def _build(self, kVals, attack_num, block, tol, max_iter, seed, **config):
-        self.dataset = config.get("dataset")
-        self.device = torch.device(config.get("device", "cuda"))
         self.kVals, self.attack_num = int(kVals), int(attack_num)
         self.block, self.tol, self.max_iter, self.seed = block, float(tol), int(max_iter), int(seed)
-        self.logger = get_logger(__name__, level=config.get("logging_level", 20))
         self.eigenvalues = self.eigenvectors = self.distances = self.predLabels = None
-        self._order = self._disSort = None
         self.iterations = 0
-        self._shape()
+        self._open(config)
 
-    def _shape(self):
-        ds = self.dataset
-        if ds is None:        # the defence workflow may hand the dataset to defense_step() instead
-            self.user_num = self.item_num = None
-        elif hasattr(ds, "info_describe") and not isinstance(ds, (tuple, list)):
-            info = ds.info_describe()
-            self.user_num, self.item_num = int(info["n_users"]), int(info["n_items"])
-        elif isinstance(ds, (tuple, list)):
-            self.user_num, self.item_num = len(ds[0]) - 1, (int(ds[3]) if len(ds) == 4 else None)
-        else:
-            self.user_num, self.item_num = int(ds.shape[0]), int(ds.shape[1])
-
-    def forward(self):
-        pass
-
-    def train_step(self, **config):
-        pass
-
-    def input_describe(self):
-        return {"defense_step": {"dataset": (object, [])}}
-
-    def output_describe(self):
-        return {"defense_step": {"spam_list": (list, [])}}
-
-    def defense_step(self, **config):
-        """PCASelectUsers.py:47-93 on the device.  `dataset=` (optional) replaces the dataset given at .I() -- the
-        workflow hands over the poisoned one it is meant to clean."""
-        if config.get("dataset") is not None:
-            self.dataset = config["dataset"]
-            self._shape()
-        if self.dataset is None:
-            raise ValueError("PCASelectUsers.defense_step: no dataset (give one to .I() or to defense_step)")
-        _lib.require_gpu()
-        U, I, rowptr, col, val = rating_csr(self.dataset, self.device)
-        self.user_num, self.item_num = U, I
+    def _detect(self, U, I, rowptr, col, val):
+        """PCASelectUsers.py:47-93 on the device."""
         if val.numel() and not bool(torch.isfinite(val).all().item()):
             raise ValueError("PCASelectUsers: the rating matrix holds non-finite values")
         k = effective_k(self.kVals, U, I)
@@ -249,22 +199,11 @@ class PCASelectUsers(BaseVictim):
         _lib.check(L.rk_pca_sq_spmv(U, I, P(rowptr), P(col), P(val), P(self.eigenvectors), k, k, P(w), P(dist), s), "rk_pca_sq_spmv")
         order = torch.empty(U, dtype=torch.int32, device=self.device)
         _lib.check(L.rk_pca_select(U, P(dist), U, P(order), s), "rk_pca_select")
-        self.distances, self._order = dist, order
-        m = flag_count(self.attack_num, U)
-        spam = order[:m].cpu().numpy().astype(np.int64)
-        self.predLabels = np.zeros(U)
-        self.predLabels[spam] = 1
+        self.distances = dist
         self.testLabels = np.zeros(U)
-        self._disSort = None
-        return spam.tolist()
+        return self._flag(order, U)
 
     @property
     def disSort(self):
         """[(user id, distance)] in ascending distance, ties to the lower id (PCASelectUsers.py:80), built on first use."""
-        if self._order is None:
-            return None
-        if self._disSort is None:
-            o = self._order.cpu().numpy()
-            d = self.distances.cpu().numpy()[o]
-            self._disSort = list(zip(o.tolist(), d.astype(np.float64).tolist()))
-        return self._disSort
+        return self._pairs(self.distances)

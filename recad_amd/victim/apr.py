@@ -33,6 +33,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._ratings import device_refusal
 from ..utils import VarDim, get_logger, pick_optim
 from .base import BaseVictim
 
@@ -160,11 +161,9 @@ class APR(BaseVictim):
         status = torch.zeros(2, dtype=torch.int32, device=dev)
         rc = _lib.lib().rk_apr_train_epoch(C.byref(desc), _lib.ptr(users), _lib.ptr(pos), _lib.ptr(neg), n, batch, self._steps_done(),
                                            1 if apply_update else 0, _lib.ptr(losses), _lib.ptr(status), _lib.stream_ptr(dev))
-        if rc != 0:
-            rule, t = status.cpu().tolist()
-            if not rule:
-                _lib.check(rc, "rk_apr_train_epoch")
-            raise ValueError(f"APR: the epoch's triplets break rule {rule} ({_lib.RK_APR_RULES.get(rule, '?')}), first in triplet {t}")
+        bad = device_refusal(rc, "rk_apr_train_epoch", status)
+        if bad:
+            raise ValueError(f"APR: the epoch's triplets break rule {bad[0]} ({_lib.RK_APR_RULES.get(bad[0], '?')}), first in triplet {bad[1]}")
         if apply_update:
             self.optimizer.state[self.weight]["step"] += n_steps
         return losses.view(n_steps, 3)

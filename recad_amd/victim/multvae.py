@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._ratings import device_refusal
 from ..utils import VarDim, get_logger, pick_optim
 from .base import BaseVictim
 
@@ -203,11 +204,9 @@ class MultVAE(BaseVictim):
         status = torch.zeros(2, dtype=torch.int32, device=dev)
         rc = _lib.lib().rk_mvae_train_epoch(C.byref(desc), _lib.ptr(ids), n, batch, step0, 1 if apply_update else 0, _lib.ptr(losses),
                                             _lib.ptr(status), _lib.stream_ptr(dev))
-        if rc != 0:
-            rule, t = status.cpu().tolist()
-            if not rule:
-                _lib.check(rc, "rk_mvae_train_epoch")
-            raise ValueError(f"Mult-VAE: the epoch's users break rule {rule} ({_lib.RK_MVAE_RULES.get(rule, '?')}), first at {t}")
+        bad = device_refusal(rc, "rk_mvae_train_epoch", status)
+        if bad:
+            raise ValueError(f"Mult-VAE: the epoch's users break rule {bad[0]} ({_lib.RK_MVAE_RULES.get(bad[0], '?')}), first at {bad[1]}")
         if apply_update:
             self.optimizer.state[self.theta]["step"] += n_steps
         return losses.view(n_steps, 3)

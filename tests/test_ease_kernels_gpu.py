@@ -129,6 +129,9 @@ def test_gram_largest_diagonal_and_its_refusal(gpu_device):
     rc, A, st = _gram(gpu_device, X, 0.5)
     assert rc == -22 and A.untouched(), "A is untouched on the refusal"
     assert st.host().tolist() == [_lib.RK_EASE_BAD_GRAM, 1] and "item 1" in _lib.lib().rk_last_error().decode()
+    X[:, 2] = X[:, 1]                              # a second item over the limit: the lower one is reported
+    rc, A, st = _gram(gpu_device, X, 0.5)
+    assert rc == -22 and A.untouched() and st.host().tolist() == [_lib.RK_EASE_BAD_GRAM, 1]
 
 
 @pytest.mark.parametrize("lam,n_items,drop", [(float("nan"), None, None), (0.0, None, None), (-1.0, None, None), (float("inf"), None, None),
@@ -183,14 +186,19 @@ def _spd(n):
 
 @pytest.mark.parametrize("block", [32, 64, 0])
 @pytest.mark.parametrize("kind,at", [("zero", 0), ("zero", 70), ("zero", 149), ("negative", 33), ("negative", 149), ("nan", 64),
-                                     ("nan", 130), ("nan_off_diagonal", (20, 101)), ("inf", 5)])
+                                     ("nan", 130), ("nan_off_diagonal", (20, 101)), ("inf", 5), ("two_zeros", (33, 120))])
 def test_invert_refuses_a_bad_pivot(gpu_device, kind, at, block):
     """150 items: the bad pivot in the first block, in a later one or in the last, partial one.  Row and column z are cleared and
-    the diagonal set, so pivot z is exactly that value; a NaN at (i, j) first reaches a pivot at max(i, j)."""
+    the diagonal set, so pivot z is exactly that value; a NaN at (i, j) first reaches a pivot at max(i, j); of two bad pivots the
+    lower is reported."""
     A = _spd(150).copy()
     if kind == "nan_off_diagonal":
         A[at] = np.nan
         z = max(at)
+    elif kind == "two_zeros":
+        z = min(at)
+        A[list(at), :] = 0
+        A[:, list(at)] = 0
     else:
         z = at
         A[z, :] = 0

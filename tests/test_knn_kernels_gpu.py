@@ -97,7 +97,7 @@ def test_norms(gpu_device, name):
 
 @pytest.mark.parametrize("name,rule", [("value0", 1), ("value128", 1), ("value2.5", 1), ("value-1", 1), ("valuenan", 1),
                                        ("duplicate", 2), ("descending", 2), ("col_n_items", 2), ("col_negative", 2),
-                                       ("two_rows", 2), ("both_rules", 1)])
+                                       ("two_rows", 2), ("same_rule_twice", 2), ("both_rules", 1)])
 def test_norms_refusals(gpu_device, name, rule):
     rows, vals, I = _norm_rows("ratings")
     ptr, idx, val = _csr(rows, vals)
@@ -117,7 +117,10 @@ def test_norms_refusals(gpu_device, name, rule):
     elif name == "two_rows":                       # the lowest offending row is reported
         idx[b + 1] = idx[b]
         val[ptr[60]] = 0.0
-    elif name == "both_rules":                     # of two rules broken in one row, the lower-numbered one
+    elif name == "same_rule_twice":                # one rule broken in two rows: the lower row
+        idx[b + 1] = idx[b]
+        idx[ptr[60] + 1] = idx[ptr[60]]
+    elif name == "both_rules":                    # of two rules broken in one row, the lower-numbered one
         idx[b + 1] = idx[b]
         val[b + 3] = 0.0
     assert R.first_violation(ptr, idx, val, I) == (rule, row)

@@ -277,6 +277,31 @@ def test_the_transpose_the_chain_relies_on(gpu_device):
     assert np.array_equal(colptr.cpu().numpy(), tp[0]) and np.array_equal(crow.cpu().numpy(), tp[1]) and np.array_equal(cval.cpu().numpy(), tp[2])
 
 
+def test_solve_rhs_reports_the_lowest_row_it_cannot_factorise(gpu_device):
+    """5 rows x 4 items, d = 2.  A NaN in item 2's factors reaches the systems of rows 1 and 3 only: the lower one is reported, in
+    either order of the rows; the clean table leaves (0, -1).  A refusal here is in the status words, the call returns 0."""
+    dev = gpu_device
+    L, p, s = _lib.lib(), _lib.ptr, _lib.stream_ptr()
+    rows = [[0, 1], [1, 2], [0, 3], [2, 3], [0]]
+    rowptr = _t(np.r_[0, np.cumsum([len(r) for r in rows])], dev, np.int32)
+    col, val = _t(np.concatenate(rows), dev, np.int32), _t(np.ones(9), dev, np.float32)
+    Y = (np.arange(8, dtype=np.float32).reshape(4, 2) + 1) / 8
+    G, rhs = _t(np.eye(2), dev, np.float32), _t(np.ones((5, 2)), dev, np.float32)
+    status = torch.full((4,), -7, dtype=torch.int32, device=dev)
+    for nan_at, order, want in ((None, None, [0, -1]), ((2, 1), None, [_lib.RK_IALS_NOT_SPD, 1]), ((2, 0), [4, 3, 2, 1, 0], [_lib.RK_IALS_NOT_SPD, 1])):
+        Yd = Y.copy()
+        if nan_at:
+            Yd[nan_at] = np.nan
+        Yt, od = _t(Yd, dev, np.float32), (None if order is None else _t(order, dev, np.int32))
+        X = Guarded(dev, 5 * 2)
+        rc = L.rk_ials_solve_rhs(5, 4, 2, p(G), p(rowptr), p(col), p(val), 1.0, p(Yt), p(rhs), p(od), _vp(X.ptr), p(status[1:3]), s)
+        torch.cuda.synchronize()
+        assert rc == 0 and status.cpu().tolist() == [-7] + want + [-7], (nan_at, order)
+        x = X.read().reshape(5, 2)
+        solved = np.array([nan_at is None or 2 not in r for r in rows])
+        assert X.untouched(np.repeat(solved, 2)) and np.all(np.isfinite(x[solved])), "a refused row is left as it was"
+
+
 def test_every_refusal_writes_nothing(gpu_device):
     dev = gpu_device
     L, p, s = _lib.lib(), _lib.ptr, _lib.stream_ptr()
